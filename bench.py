@@ -2,6 +2,7 @@
 """Benchmark: TDA A.x throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config H|C1..C5|C4d]
+                    [--dump-outputs DIR] [--full]
 
 With ``--gpus N > 1`` outside a torch.distributed launch, this process starts
 ``torch.distributed.run`` with N ranks (one process per GPU, RCCL over xGMI)
@@ -22,11 +23,21 @@ aux window + a row block of the stored exchange per rank (``DeviceOperator``
 partition); each rank computes a partial sigma of all vectors, one all-reduce
 sums them: fixed total work, "scaling": "strong".
 
-Extra JSON fields: roofline (dominant GEMM class timed live with HIP events on
-the library's stream over the timed steps; traffic from this config's committed
-rocprofv3 PMC summary), cpu_baseline (the NumPy oracle = the reference's AO
-route, timed on this host's cores), converge (wall time of the device Davidson
-to nroots with the reference's criteria, including operator construction).
+A plain run sets up, warms up, times the K steps and prints the result line.
+Its extra JSON fields come from the timed steps themselves: roofline and
+gemm_classes (GEMM classes timed live with HIP events on the library's stream
+over the timed steps; traffic from this config's committed rocprofv3 PMC
+summary).  ``--dump-outputs DIR`` also writes the last timed step's sigma
+vectors to ``DIR/sigma.npy`` (float64; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output).
+
+``--full`` adds everything that takes runs of its own after the timed steps:
+check (symmetry of the measured operator), ranks (per-rank phase split),
+cpu_baseline + verify (the NumPy oracle = the reference's AO route, timed on
+this host's cores, and its sigma against the device's), converge (wall time of
+the device Davidson to nroots with the reference's criteria, including operator
+construction).  ``--no-cpu-baseline`` / ``--no-converge`` / ``--cpu-converge``
+select among them and mean nothing without ``--full``.
 
 ``XT_BENCH_OPERATOR=module:function`` replaces the operator factory (the CPU
 launcher test uses a stub from tests/); ``XT_BENCH_BACKEND=gloo`` rehearses the
@@ -114,6 +125,12 @@ def parse(argv=None):
                          "rate puts it under CPU_CONVERGE_AUTO_S)")
     ap.add_argument("--k-mode", default="auto", choices=["auto", "direct", "stored"],
                     help="exchange evaluation (xt_set_exchange_mode)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks and side measurements: symmetry check, "
+                         "per-rank phase split, CPU baseline + verify, Davidson convergence "
+                         "(--no-cpu-baseline / --no-converge / --cpu-converge select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the sigma vectors of the last timed step to DIR/sigma.npy (float64)")
     args = ap.parse_args(argv)
     preset = dict(sa=0, remove=False, jk="DF", ngrid=None, method=0)
     preset.update(CONFIGS[args.config])
@@ -618,6 +635,26 @@ def breakdown(op, z, out, allreduce, sync, stats_acc, steps, rank, world, reps=2
                 kernel_ms={k: round(v["ms"] / steps, 3) for k, v in stats_acc.items() if v["launches"]})
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6   # --dump-outputs: everything written stays under this
+DUMP_SEED = 20261019
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: ``sigma.npy`` = what a caller of the timed step receives, the (nvec, dim)
+    float64 sigma vectors of the last timed step (all-reduced when N > 1).  An output above
+    DUMP_MAX_BYTES is written as a fixed sample instead: its elements (flattened, row-major) at
+    sorted positions drawn once from numpy's default_rng(DUMP_SEED), the same for every run of
+    the same shape."""
+    os.makedirs(path, exist_ok=True)
+    s = out.detach().cpu().numpy().astype(np.float64, copy=False)
+    keep = DUMP_MAX_BYTES // 8 - 64            # (room for the .npy header)
+    if s.size > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(s.size, size=keep, replace=False))
+        s = s.reshape(-1)[idx]
+    np.save(os.path.join(path, "sigma.npy"), s)
+    log(f"last timed step's sigma written to {os.path.join(path, 'sigma.npy')}: shape {s.shape}")
+
+
 def rank_main(args):
     import torch
     import torch.distributed as dist
@@ -694,8 +731,11 @@ def rank_main(args):
     dt = time.perf_counter() - t0
     op.set_profile(0)
     phases = op.last_timings()          # the last timed step's phase split
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    full = args.full                     # everything beyond the headline figure
     z0 = s0 = None
-    if use_gpu:                          # the first timed vector and its device sigma (verify)
+    if use_gpu and full:                 # the first timed vector and its device sigma (verify)
         z0, s0 = z[:1].cpu().numpy(), out[:1].cpu().numpy()
     # RCCL reduces device tensors only (a host tensor raises under the nccl backend)
     tt = torch.tensor([dt], dtype=torch.float64,
@@ -704,12 +744,11 @@ def rank_main(args):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     T = float(tt.item())
     log(f"timed {args.steps} steps: {1e3 * T / args.steps:.2f} ms per step")
-    verify = w.verify(z, out) if hasattr(w, "verify") else None   # a workload's own self-check
+    verify = w.verify(z, out) if (full and hasattr(w, "verify")) else None   # a workload's own self-check
     # outside the timed region: A is symmetric, so <y, A x> = <A y, x> on the measured
     # operator itself (two 2-vector A.x calls, all-reduced like the timed ones)
     symmetry = None
-    if use_gpu:
-        import torch
+    if use_gpu and full:
         gs = torch.Generator(device=w.device)
         gs.manual_seed(7)
         xv = torch.randn((2, op.dim), dtype=torch.float64, device=w.device, generator=gs)
@@ -718,7 +757,7 @@ def rank_main(args):
         lhs, rhs = yv @ ax.T, ay @ xv.T
         symmetry = float((lhs - rhs).abs().max() / lhs.abs().max())
     # per-rank breakdown (outside the timed region: synchronised after each phase)
-    mine = breakdown(op, z, out, allreduce_sigma, sync, stats_acc, args.steps, rank, world)
+    mine = breakdown(op, z, out, allreduce_sigma, sync, stats_acc, args.steps, rank, world) if full else None
     roofline = roofline_of(args, stats_acc, args.steps, world)
     others = {}
     for k, v in stats_acc.items():
@@ -768,12 +807,12 @@ def rank_main(args):
     if symmetry is not None:
         result["check"] = dict(symmetry_rel=symmetry,
                                what="max |<y,Ax> - <Ay,x>| / max |<y,Ax>| over 2 x 2 random vectors")
-    if rank == 0 and world == 1 and use_gpu and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and use_gpu and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"], result["verify"] = cpu_baseline(args, w, z0, s0)
         except Exception as e:   # report, never hide
             result["cpu_baseline"] = dict(value=None, error=repr(e))
-    if use_gpu and (not args.no_converge or args.converge):
+    if full and use_gpu and (not args.no_converge or args.converge):
         result["converge"] = converge(args, w, allreduce_sigma, world)
         mine["converge"] = {k: result["converge"][k] for k in ("ax_s", "allreduce_s", "host_davidson_s")}
         cpu = result.get("cpu_baseline") or {}
@@ -787,11 +826,11 @@ def rank_main(args):
             result["cpu_baseline"] = cpu
         elif rank == 0 and world == 1 and est is not None:
             cpu["converge"] = dict(skipped=f"estimated {est:.0f} s of CPU A.x (--cpu-converge on runs it)")
-    if pg:
+    if full and pg:
         ranks = [None] * world
         dist.all_gather_object(ranks, mine)
         result["ranks"] = ranks
-    else:
+    elif full:
         result["ranks"] = [mine]
     if rank == 0:
         print(json.dumps(result), flush=True)

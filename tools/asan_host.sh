@@ -23,7 +23,7 @@ for p in "${pids[@]}"; do wait "$p" || { echo "asan compile failed"; exit 1; }; 
 echo 'const char* xt_build_id(void) { return "asan-host-build"; }' > "$OUT/xt_build_id.c"
 gcc -O1 -fPIC -c "$OUT/xt_build_id.c" -o "$OUT/xt_build_id.o"
 objs+=("$OUT/xt_build_id.o")
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -fsanitize=address -o "$OUT/libxtddft_amd_asan.so" "${objs[@]}"
-/opt/rocm/lib/llvm/bin/clang++ -O1 -g -fsanitize=address -fno-omit-frame-pointer tests/asan/asan_driver.cpp \
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -Xarch_host -fsanitize=address -o "$OUT/libxtddft_amd_asan.so" "${objs[@]}"
+/opt/rocm/lib/llvm/bin/clang++ -O1 -g -fsanitize=address -fno-gpu-sanitize -Wno-unused-command-line-argument -fno-omit-frame-pointer tests/asan/asan_driver.cpp \
   -L"$OUT" -lxtddft_amd_asan -Wl,-rpath,"$(pwd)/$OUT" -o "$OUT/asan_driver"
 ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 "$OUT/asan_driver"

@@ -16,7 +16,7 @@ for c in ${CONFIGS:-H}; do
   D="$OUT/$c"
   mkdir -p "$D"
   if [ -z "${SKIP_BENCH:-}" ]; then
-    timeout -k 10 ${BENCH_LIMIT:-600} python3 -u bench.py --config "$c" ${BENCH_ARGS:-} > "$D/bench.log" 2>&1
+    timeout -k 10 ${BENCH_LIMIT:-600} python3 -u bench.py --full --config "$c" ${BENCH_ARGS:-} > "$D/bench.log" 2>&1
     rc=$?; echo "[$c] bench rc=$rc: $(tail -c 300 "$D/bench.log" | tr -d '\n' | tail -c 200)"
     [ $rc = 0 ] || exit $rc
   fi
