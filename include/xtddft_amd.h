@@ -206,6 +206,45 @@ int xt_row_norms2(int nrow, int dim, const double* x, double* out, void* hip_str
 /* x[i,:] *= s[i] */
 int xt_row_scale(int nrow, int dim, double* x, const double* s, void* hip_stream);
 
+/* State-to-state transition moments of spin-flip amplitudes: out[x,i,j] =
+   <state i| op_x |state j> for the roots of an XSF / SF-TDA solve (replaces the
+   nstates^2 x 3 x 16 trace terms of XSF_TDA.calculate_TDM_R / calculate_TDM_U,
+   XSF_TDA.py:435-592, and the moment loop of XSF_TDA_GPU.osc_str, XSF_TDA_GPU.py:936-1116).
+   A state is the (nc+no) x (no+nv) amplitude matrix c (rows: occupied [c|o], columns:
+   virtual [o|v]); with D_occ = c_occ^T op c_occ and D_vir = c_vir^T op c_vir the 16 terms
+   are T[i,j] = sum c_i o (D c_j), D a symmetric linear map applied once per state:
+     Y[c rows] = c[c rows] D_vir^(f1),  Y[o rows] = c[o rows] D_vir^(f2),
+     Y[:, o cols] -= D_occ^(f2) c[:, o cols],  Y[:, v cols] -= D_occ^(f1) c[:, v cols],
+     Y_co += f3 tr(oo) D_occ[c,o],  Y_ov -= f3 tr(oo) D_vir[o,v],
+     Y_oo += f3 I (sum D_occ[c,o] o co - sum D_vir[o,v] o ov),
+   M^(f) = M with its off-diagonal blocks (c<->o of D_occ, o<->v of D_vir) times f.
+   sa = 0 (and every UKS reference): f = (1, 1, 0); otherwise, S = si (XSF_TDA.py:496-507),
+   f1 = sqrt((2S+1)/2S), f2 = sqrt(2S/(2S-1)), f3 = 1/sqrt(2S(2S-1)).
+   The AO->MO transforms, the pack of the vector rows into c, D for every component and
+   state and the Gram contraction all run on the device inside the call; the products go
+   through the engine behind xt_dgemm.  Reductions are fixed-order: two calls on the same
+   input return the same bits.  The workspace lives for the call only; the part that grows
+   with nstates is capped (768 MiB; states are processed in chunks). */
+#define XT_TDM_LAYOUT_OV 0      /* a vector row is c itself, occ x vir row-major (PySCF's
+                                   spin-flip order, SF_TDA.py:224-243) */
+#define XT_TDM_LAYOUT_BLOCKS 1  /* the reference's cv|co|ov|oo blocks (XSF_TDA.py:509-515),
+                                   OO compressed by vects when oo_compressed */
+typedef struct xt_tdm_desc {
+  int nao;
+  int nc, no, nv;      /* c rows = nc + no, columns = no + nv (no = 0: SF-up, beta -> alpha) */
+  int ncomp;           /* operator components (3 for a dipole) */
+  int nstates;
+  int sa;              /* 0: f = (1, 1, 0); != 0: the spin-adapted factors of si */
+  double si;           /* S of the reference (mol.spin / 2) */
+  int layout;          /* XT_TDM_LAYOUT_* */
+  int oo_compressed;   /* block layout: the OO block holds no^2 - 1 coefficients of vects */
+} xt_tdm_desc;
+/* op_ao (ncomp, nao, nao) symmetric; c_occ (nao, nc+no); c_vir (nao, no+nv); vecs
+   (nstates, dim) row-major; vects (no^2, no^2-1) or null; out (ncomp, nstates, nstates).
+   All pointers of one ptr_kind. */
+int xt_tdm(const xt_tdm_desc* desc, const double* op_ao, const double* c_occ, const double* c_vir,
+           const double* vecs, const double* vects, double* out, int ptr_kind, void* hip_stream);
+
 /* mean-field front end ------------------------------ */
 /* 3-index Coulomb integrals (ab|c) over contracted Cartesian Gaussians by
    McMurchie-Davidson (replaces libcint int3c2e behind PySCF df.incore.aux_e2,

@@ -30,7 +30,7 @@ EXPORTS = [
     "xt_set_grid", "xt_set_oo_basis", "xt_apply", "xt_dim", "xt_last_timings",
     "xt_xsf_j_diagonals", "xt_set_exchange_mode", "xt_prepare", "xt_exchange_plan", "xt_set_partition", "xt_set_profile",
     "xt_profile_stats", "xt_profile_bytes", "xt_dgemm", "xt_dgemm_strided", "xt_precond", "xt_row_norms2", "xt_row_scale", "xt_build_id",
-    "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao",
+    "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao", "xt_tdm",
 ]
 
 
@@ -41,6 +41,16 @@ class XtDesc(ctypes.Structure):
         ("xctype", c_int), ("hyb", c_double), ("alpha", c_double), ("omega", c_double),
         ("si", c_double), ("sa", c_int), ("foo", c_double), ("fglobal", c_double),
         ("remove", c_int), ("add_local", c_int), ("device", c_int), ("sf_kernel", c_int),
+    ]
+
+
+TDM_LAYOUT = {"ov": 0, "blocks": 1}   # XT_TDM_LAYOUT_*
+
+
+class XtTdmDesc(ctypes.Structure):
+    _fields_ = [
+        ("nao", c_int), ("nc", c_int), ("no", c_int), ("nv", c_int), ("ncomp", c_int),
+        ("nstates", c_int), ("sa", c_int), ("si", c_double), ("layout", c_int), ("oo_compressed", c_int),
     ]
 
 
@@ -109,6 +119,7 @@ def lib():
     L.xt_int2e_cart.argtypes = [c_int, vp, dp, dp, c_int, vp, dp, dp, c_int, c_int, c_double, dp, dp, c_double,
                                 c_int, dp, c_long, vp]
     L.xt_eval_ao.argtypes = [c_int, dp, c_int, vp, dp, dp, dp, c_int, dp, c_long, c_long, vp]
+    L.xt_tdm.argtypes = [POINTER(XtTdmDesc), dp, dp, dp, dp, dp, dp, c_int, vp]
     for name in EXPORTS:
         if not hasattr(L, name):
             raise LibraryMissing(f"{LIB_PATH} lacks symbol {name}")

@@ -32,6 +32,7 @@ using namespace xt;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
+int xt::set_error(int code, const char* msg) { return fail(code, msg); }
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) \
     return fail(XT_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e)); } while (0)
 #define RET(x) do { int _r = (x); if (_r) return _r; } while (0)

@@ -12,6 +12,9 @@
 
 namespace xt {
 
+// records the message xt_last_error() returns (xt_ctx.hip) and hands the code back
+int set_error(int code, const char* msg);
+
 // Buffer descriptor over a wave-uniform base (readfirstlane'd so the compiler can prove it:
 // cdna_hip_programming.md T20); loads through it take a 32-bit lane offset and a scalar one,
 // so no 64-bit address arithmetic runs on the VALU.  The range is 2 GB from the base.

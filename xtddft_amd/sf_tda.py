@@ -186,6 +186,36 @@ class _SFBase:
             self.e, self.v = scipy.linalg.eigh(self.A)
         return self.e[:nstates] * HA2EV, self.v[:, :nstates]
 
+    # ------------------------------------------------ state-to-state moments
+    def transition_dipoles(self, op_ao=None):
+        """(ncomp, N, N) moments <i|op|j> between the ``nstates`` roots of the last
+        ``kernel``, through the device entry ``xt_tdm``.  The reference has no such method
+        on the SF-TDA classes; the formula is ``XSF_TDA.calculate_TDM_U``'s
+        (XSF_TDA.py:435-478), tr(c_i D_vir c_j^T) - tr(c_i^T D_occ c_j), which is generic for
+        a spin-flip amplitude matrix: f = (1, 1, 0).  SF-down: alpha occupied -> beta virtual
+        in cv|co|ov|oo order; SF-up: beta occupied (nc) -> alpha virtual (nv), no open block.
+        ``op_ao`` (ncomp, nao, nao) symmetric, default ``int1e_r`` at the centre of nuclear
+        charge.  A sharded run computes the same replicated result on every rank."""
+        from . import tdm
+        if op_ao is None:
+            op_ao = tdm.charge_centre_dipole(self.mf)
+        _, mo_occ, mo_coeff = mf_info(self.mf)
+        vecs = np.asarray(self.v)[:, :self.nstates].T
+        if self.isf == -1:
+            c_occ, c_vir = mo_coeff[0][:, mo_occ[0] > 0], mo_coeff[1][:, mo_occ[1] == 0]
+            return tdm.transition_moments(op_ao, c_occ, c_vir, vecs, self.nc, self.no, self.nv,
+                                          layout="blocks", device=self.device)
+        c_occ, c_vir = mo_coeff[1][:, mo_occ[1] > 0], mo_coeff[0][:, mo_occ[0] == 0]
+        return tdm.transition_moments(op_ao, c_occ, c_vir, vecs, self.nc, 0, self.nv,
+                                      layout="ov", device=self.device)
+
+    def osc_str(self, op_ao=None):
+        """N x N oscillator strengths (2/3) |e_i - e_j| sum_x T_x[i,j]^2 between the roots
+        (the expression of XSF_TDA.py:591)."""
+        from . import tdm
+        t = self.transition_dipoles(op_ao)
+        return tdm.osc_matrix(np.asarray(self.e)[:t.shape[1]], t)
+
 
 class SF_TDA_up(_SFBase):
     isf = 1

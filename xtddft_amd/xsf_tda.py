@@ -298,6 +298,52 @@ class XSF_TDA:
             print("\n".join(lines))
         return Ds, lines
 
+    # ------------------------------------------------ state-to-state moments
+    def transition_dipoles(self, op_ao=None):
+        """(ncomp, N, N) moments <i|op|j> between the roots of the last ``kernel``
+        (``calculate_TDM_R`` / ``calculate_TDM_U``, XSF_TDA.py:435-592) through the device
+        entry ``xt_tdm``.  ROKS: the spin-adapted factors of ``self.SA`` with S =
+        ``ground_s``, a compressed OO block expanded by ``self.vects``; UKS: the alpha
+        occupied / beta virtual sets with f = (1, 1, 0).  ``op_ao`` (ncomp, nao, nao), any
+        symmetric AO operator, defaults to ``int1e_r`` at the centre of nuclear charge
+        (XSF_TDA.py:482-487).  A sharded run computes the same replicated result on every
+        rank (no collective)."""
+        from . import tdm
+        if op_ao is None:
+            op_ao = tdm.charge_centre_dipole(self.mf)
+        nc, no, nv = self.nc, self.no, self.nv
+        vecs = np.asarray(self.v).T
+        vects = self.vects if self.re else None
+        if vecs.shape[1] != (nc + no) * (no + nv) - (1 if self.re else 0):
+            raise ValueError("the roots do not span the full cv|co|ov|oo space (frozen core?)")
+        if self.type_u:
+            ca, cb = self.mf.mo_coeff
+            c_occ, c_vir = ca[:, self.mo_occ[0] > 0], cb[:, self.mo_occ[1] == 0]
+            sa, si = 0, 0.0
+        else:
+            c = self.mf.mo_coeff
+            c_occ, c_vir = c[:, :nc + no], c[:, nc:]
+            sa, si = self.SA, self.ground_s
+        return tdm.transition_moments(op_ao, c_occ, c_vir, vecs, nc, no, nv, sa=sa, si=si,
+                                      layout="blocks", vects=vects, device=self.device)
+
+    def osc_str(self, op_ao=None):
+        """N x N oscillator strengths (2/3) |e_i - e_j| sum_x T_x[i,j]^2 between the roots
+        (``XSF_TDA_GPU.osc_str``, XSF_TDA_GPU.py:936-1116; XSF_TDA.py:591)."""
+        from . import tdm
+        t = self.transition_dipoles(op_ao)
+        return tdm.osc_matrix(np.asarray(self.e)[:t.shape[1]], t)
+
+    def calculate_TDM(self, verbose=True):
+        """``(tdm, osc)`` with the default dipole operator; prints the reference's table
+        (XSF_TDA.py:493-494, 592) when ``verbose``."""
+        from . import tdm
+        t = self.transition_dipoles()
+        osc = tdm.osc_matrix(np.asarray(self.e)[:t.shape[1]], t)
+        if verbose:
+            print("\n".join(tdm.tdm_table(t, osc)))
+        return t, osc
+
     def get_Amat(self, foo=1.0, fglobal=None):
         """Explicit (remove-compressed when self.re) A through the device operator."""
         vind, _ = self.gen_tda_operation_sf(foo, fglobal)
