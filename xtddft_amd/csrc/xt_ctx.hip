@@ -101,7 +101,13 @@ struct xt_ctx {
   int kr0 = 0, kr1 = -1;         // -1: all O rows
   bool trimmed = false;          // the MO factor holds only this rank's aux window (xt_prepare)
   int naux_full = 0;             // desc naux before the trim
+  size_t chunk_bytes = 0;        // XT_CHUNK_BYTES: cap on every chunk-loop byte budget (0: not set)
 };
+
+// byte budget of a chunked loop: its default, capped by XT_CHUNK_BYTES when that is set
+static inline size_t chunk_budget(const xt_ctx* c, size_t dflt) {
+  return (c->chunk_bytes > 0 && c->chunk_bytes < dflt) ? c->chunk_bytes : dflt;
+}
 
 // a factor setter after a trim starts over with the full aux count (both factors must be set again)
 static void untrim(xt_ctx* c) {
@@ -250,8 +256,9 @@ int xt_create(const xt_desc* desc, xt_ctx** out) {
   }
   for (int i = 0; i < 5; ++i) (void)hipEventCreate(&c->ev[i]);
   {
-    // the only environment knobs, read here once per context: which XC kernels run the
-    // fused classes outside their automatic ranges (tests/test_gpu_variants.py).
+    // the only environment knobs, read here once per context (test hooks): which XC kernels
+    // run the fused classes outside their automatic ranges (tests/test_gpu_variants.py), and
+    // XT_CHUNK_BYTES below.
     // Defaults: dedicated M-backward for O <= 128, rho-forward for O > 64 and the
     // small-O rho-forward for O <= 48 (from 8 trial pairs), the engine's fused modes
     // otherwise (where they win or the dedicated kernels do not fit).  XT_W_KERNEL: 0 the
@@ -260,6 +267,14 @@ int xt_create(const xt_desc* desc, xt_ctx** out) {
     c->m_kernel = !(em && atoi(em) == 0);
     const char* ew = getenv("XT_W_KERNEL");
     c->w_kernel = ew ? (atoi(ew) == 0 ? 0 : atoi(ew) == 3 ? 3 : 1) : 2;
+    // XT_CHUNK_BYTES (tests/test_gpu_chunks.py): caps the byte budgets of the chunked loops
+    // over grid points and aux rows (xt_set_grid, df_to_mo, sandwich, exchange_main,
+    // xc_response) so that small problems run several chunks and a ragged last one.  Unset
+    // or <= 0: every budget is its default; the floors (one aux row, one grid row, 64 XC
+    // points) hold either way
+    const char* ec = getenv("XT_CHUNK_BYTES");
+    const long long cb = ec ? atoll(ec) : 0;
+    c->chunk_bytes = cb > 0 ? (size_t)cb : 0;
   }
   *out = c;
   return 0;
@@ -360,7 +375,7 @@ static int df_to_mo(xt_ctx* c, const double* cderi, int np_total, DevBuf& dst, i
       HIPCHK(hipMemsetAsync(dst.p + ((size_t)b * naux_rows + np_total) * mm, 0,
                             (size_t)(naux_rows - np_total) * mm * 8, c->st));
   if (np_total <= 0) return 0;
-  const size_t budget = (size_t)2 << 30;   // bytes per staging buffer
+  const size_t budget = chunk_budget(c, (size_t)2 << 30);   // bytes per staging buffer
   int pc = (int)(budget / (8 * (aa > mm ? aa : mm)));
   if (pc < 1) pc = 1;
   if (pc > np_total) pc = np_total;
@@ -514,8 +529,9 @@ int xt_set_grid(xt_ctx* c, const double* ao, const double* w, const double* kern
   const size_t phi_used = (size_t)c->nbasis * ncomp * ng * nmo;
   RET(c->Phi.ensure(phi_used + (size_t)XC_GRID_SLACK * nmo));
   HIPCHK(hipMemsetAsync(c->Phi.p + phi_used, 0, (c->Phi.n - phi_used) * sizeof(double), c->st));
-  const size_t gchunk_max = ((size_t)1 << 30) / (8 * (size_t)nao);
-  const int gc = (int)(gchunk_max < (size_t)ng ? gchunk_max : ng);
+  const size_t gchunk_max = chunk_budget(c, (size_t)1 << 30) / (8 * (size_t)nao);
+  int gc = (int)(gchunk_max < (size_t)ng ? gchunk_max : ng);
+  if (gc < 1) gc = 1;
   if (ptr_kind == XT_PTR_HOST) RET(c->stage.ensure((size_t)gc * nao));
   for (int comp = 0; comp < ncomp; ++comp) {
     for (int g0 = 0; g0 < ng; g0 += gc) {
@@ -589,7 +605,7 @@ static int sandwich(xt_ctx* c, const double* Bo, const double* Bv, int nz,
   const long mm = (long)nmo * nmo;
   const double left = 2.0 * nry * nrx * (double)nz * ncx + 2.0 * nry * (double)nz * ncx * ncy;
   const double right = 2.0 * (double)nz * nrx * ncx * ncy + 2.0 * nry * nrx * (double)nz * ncy;
-  const size_t budget = (size_t)3 << 30;
+  const size_t budget = chunk_budget(c, (size_t)3 << 30);
   if (left <= right) {
     // T[P] (nry, nz, ncx) = Bo[P,rows] . Zr ; out(nry,nz,ncy) += T . Bv[P,cols]
     const size_t per = (size_t)nry * nz * ncx;
@@ -728,7 +744,7 @@ static int exchange_main(xt_ctx* c, int nz, const DevBuf& B, double coef) {
   for (int q = 0; q < ngr; ++q) {
     const int nzg = gr[q].nch * nz;
     const size_t per = (size_t)O * nzg * V;
-    int pc = (int)(((size_t)3 << 30) / (8 * per));
+    int pc = (int)(chunk_budget(c, (size_t)3 << 30) / (8 * per));
     if (pc < 1) pc = 1;
     if (pc > naux) pc = naux;
     RET(c->tbuf.ensure((size_t)pc * per));
@@ -1044,7 +1060,7 @@ static int xc_response(xt_ctx* c, int nz) {
   Group gr[2];
   const int ngr = channel_groups(c, gr);
   const size_t per_g = (size_t)nch * nz * O * (mgga ? 4 : 1) + (gga ? (size_t)nch * nz * 3 : 0);
-  size_t G = ((size_t)8 << 30) / (8 * per_g);
+  size_t G = chunk_budget(c, (size_t)8 << 30) / (8 * per_g);
   if (G > (size_t)ng) G = ng;
   if (G < 64) G = 64 < (size_t)ng ? 64 : ng;
   RET(c->ubuf.ensure((size_t)nch * nz * O * G));

@@ -12,8 +12,6 @@ void permute_add_strided(hipStream_t st, int nz, int nry, int ncy, double alpha,
 void xsf_rank1(hipStream_t st, int nz, int nc, int no, int nv, int nmo, double a2, double a4,
                const double* ze, const double* fs, const double* fa, const double* fb, double* acc);
 void ediag(hipStream_t st, int nz, int O, int V, int nmo, int v0, const double* eps, const double* ze, double* acc);
-void xc_uks(hipStream_t st, int ncomp, int G, int g0, int ngrid, int nz, int O, int nmo,
-            const double* phi0, const double* phi1, const double* wfxc, double* U);
 // ns = 2: both spin channels of the UKS response (kernel (2, nk, 2, nk, ngrid)); ns = 1: one
 // spin-flip channel with the multicollinear kernel (nk, nk, ngrid); U1 / R1 / pO1 unused
 void xc_uks_w(hipStream_t st, int ns, int ncomp, int G, int g0, int ngrid, int nz, int O, int nmo, long compP,

@@ -182,87 +182,6 @@ __global__ void k_ediag(int nz, int O, int V, int nmo, int v0, const double* __r
   }
 }
 
-// ---- XC response on the grid, UKS kernel (PySCF nr_uks_fxc semantics) ----
-// For each grid point g and vector x (one 64-lane wave):
-//   rho1[s][0]  = sum_i U0[s][g][x,i] * PhiO0[s][g][i]
-//   rho1[s][c]  = sum_i (U0 PhiOc + Uc PhiO0)        c = 1..3 (GGA)
-//   wv[s][y]    = sum_{t,y'} wfxc[t,y'][s,y][g] rho1[t][y']   (weight folded in)
-//   S0[s][g][x,i] = wv0 PhiO0 + sum_c wvc PhiOc ;  Sc = wvc PhiO0
-// U is overwritten by S.  U layout: (nch, ncomp, G, nz*O); PhiO of channel s
-// is phi[s] + comp*ngrid*nmo + (g0+g)*nmo + i.
-template <int NC>
-__global__ void __launch_bounds__(256)
-k_xc_uks(int G, int g0, int ngrid, int nz, int O, int nmo,
-         const double* __restrict__ phi0, const double* __restrict__ phi1,
-         const double* __restrict__ wfxc, double* __restrict__ U) {
-  const int lane = threadIdx.x & 63;
-  const long wid = (blockIdx.x * (long)blockDim.x + threadIdx.x) >> 6;
-  const long nwork = (long)G * nz;
-  if (wid >= nwork) return;
-  const int g = (int)(wid / nz);
-  const int x = (int)(wid % nz);
-  const long ldU = (long)nz * O;
-  const long compU = (long)G * ldU;
-  const long chU = NC * compU;
-  const long compP = (long)ngrid * nmo;
-  const double* phis[2] = {phi0, phi1};
-
-  double rho[2][NC];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const double* ph = phis[s] + (long)(g0 + g) * nmo;
-    const double* u = U + s * chU + (long)g * ldU + (long)x * O;
-    double acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-    for (int i = lane; i < O; i += 64) {
-      const double u0 = u[i];
-      const double p0 = ph[i];
-      acc[0] += u0 * p0;
-#pragma unroll
-      for (int c = 1; c < NC; ++c)
-        acc[c] += u0 * ph[c * compP + i] + u[c * compU + i] * p0;
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      double v = acc[c];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-      rho[s][c] = v;
-    }
-  }
-  // wv[s][y] = sum_{t,y'} f[t,y',s,y] rho[t][y']  ; f layout (2,NC,2,NC,ngrid)
-  double wv[2][NC];
-  const long gg = g0 + g;
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int y = 0; y < NC; ++y) {
-      double v = 0.0;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int yy = 0; yy < NC; ++yy)
-          v += wfxc[((((long)t * NC + yy) * 2 + s) * NC + y) * ngrid + gg] * rho[t][yy];
-      wv[s][y] = v;
-    }
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const double* ph = phis[s] + (long)(g0 + g) * nmo;
-    double* u = U + s * chU + (long)g * ldU + (long)x * O;
-    for (int i = lane; i < O; i += 64) {
-      const double p0 = ph[i];
-      double s0 = wv[s][0] * p0;
-#pragma unroll
-      for (int c = 1; c < NC; ++c) {
-        s0 += wv[s][c] * ph[c * compP + i];
-        u[c * compU + i] = wv[s][c] * p0;
-      }
-      u[i] = s0;
-    }
-  }
-}
-
 // ---- XC response, "W route" (one 256-thread block per grid point g) ---------
 // Spin channel s of trial vector x holds, at grid point g (g0 + g globally):
 //   U_s[g][x*O + i] = sum_a PhiV0[g][a] Z[x][i][a]       (GEMM, xc forward)
@@ -1016,15 +935,6 @@ void xsf_rank1(hipStream_t st, int nz, int nc, int no, int nv, int nmo, double a
 }
 void ediag(hipStream_t st, int nz, int O, int V, int nmo, int v0, const double* eps, const double* ze, double* acc) {
   hipLaunchKernelGGL(k_ediag, dim3(nblocks(2L * nz * O * V)), dim3(256), 0, st, nz, O, V, nmo, v0, eps, ze, acc);
-}
-void xc_uks(hipStream_t st, int ncomp, int G, int g0, int ngrid, int nz, int O, int nmo,
-            const double* phi0, const double* phi1, const double* wfxc, double* U) {
-  const long waves = (long)G * nz;
-  const int blocks = (int)((waves * 64 + 255) / 256);
-  if (ncomp == 4)
-    hipLaunchKernelGGL(k_xc_uks<4>, dim3(blocks), dim3(256), 0, st, G, g0, ngrid, nz, O, nmo, phi0, phi1, wfxc, U);
-  else
-    hipLaunchKernelGGL(k_xc_uks<1>, dim3(blocks), dim3(256), 0, st, G, g0, ngrid, nz, O, nmo, phi0, phi1, wfxc, U);
 }
 // Meta-GGA point kernel (nr_uks_fxc's MGGA branch, XTDA.py:514; explicit form
 // XTDA.py:239-276): the GGA contraction above plus the kinetic-energy density,
