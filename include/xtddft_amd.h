@@ -245,6 +245,46 @@ typedef struct xt_tdm_desc {
 int xt_tdm(const xt_tdm_desc* desc, const double* op_ao, const double* c_occ, const double* c_vir,
            const double* vecs, const double* vects, double* out, int ptr_kind, void* hip_stream);
 
+/* Transition moments between spin-conserving roots (X-TDA / U-TDA) and from the reference
+   state to them: out[x,L,R] = <state L| op_x |state R> (replaces the nstates^2 calls of
+   TDM_S and the nstates calls of TDM_GSS / TDM_SGS, x2c_hamiltonian/driver/tdm.py:6-126,
+   that X_TDA.calculate_TDM loops over, xtddft/XTDA.py:1354-1400, and the host einsum of
+   XTDA._transition).  A state is a row of vecs in the solver's own (PySCF) order [za | zb]:
+   A = za (nocc_a x nvir_a), B = zb (nocc_b x nvir_b).  With d^a = C_a^T op C_a and
+   d^b = C_b^T op C_b,
+     T[L,R]  = tr(A_L d^a_vv A_R^T) - tr(A_L^T d^a_oo A_R)
+             + tr(B_L d^b_vv B_R^T) - tr(B_L^T d^b_oo B_R)                  (all of U-TDA)
+     T[0,R]  = T[R,0] = <d^a_ov, A_R> + <d^b_ov, B_R>,  T[0,0] = 0          (with_ground)
+   and, for spin_adapted with no > 0 (ROKS: rows of A = [c|o], columns of B = [o|v]), in the
+   spin-tensor basis of utils.so2st, cv1 = (A[c rows] - B[:, v columns]) / sqrt(2),
+   co = B[:, o columns], ov = A[o rows]:
+     T[L,R] -= h (sum co^L_iu d_ub cv1^R_ib + sum ov^L_ua d_ju cv1^R_ja) + (L <-> R),
+     h = sqrt((S+1)/(2S)) - 1/sqrt(2),  d_ub = d^b_vv[o,v],  d_ju = d^a_oo[c,o].
+   Phase: in so2st's phase the four couplings of CV(1) with CO(0) and OV(0) carry
+   -sqrt((S+1)/(2S)); tdm.py:116-125 writes + because its CV(1) has the opposite sign.
+   The form is bilinear, so Y_R = dT/dz_L is built once per state (engine GEMMs on the rows
+   of vecs in place, small kernels for cv1 and its scatter) and one Gram product over dim
+   gives every pair.  Reductions are fixed-order: two calls on the same input return the same
+   bits.  The workspace lives for the call; the part that grows with nstates is capped
+   (768 MiB, XT_TDM_WS_MIB lowers it; states are processed in chunks). */
+typedef struct xt_tdm_sc_desc {
+  int nao;
+  int nocc_a, nvir_a, nocc_b, nvir_b;   /* za (nocc_a x nvir_a), zb (nocc_b x nvir_b) */
+  int ncomp;          /* operator components (3 for a dipole) */
+  int nstates;
+  int spin_adapted;   /* 0: spin-orbital formula (U-TDA); 1: the X-TDA correction */
+  int no;             /* spin_adapted: open shells; nocc_a - nocc_b = nvir_b - nvir_a = no */
+  double si;          /* S of the reference, > 0 when spin_adapted and no > 0 */
+  int with_ground;    /* 1: row / column 0 is the reference state */
+} xt_tdm_sc_desc;
+/* op_ao (ncomp, nao, nao) symmetric; c_occ_a (nao, nocc_a), c_vir_a (nao, nvir_a), c_occ_b
+   (nao, nocc_b), c_vir_b (nao, nvir_b) (a block with no columns may be null); vecs (nstates,
+   nocc_a nvir_a + nocc_b nvir_b) row-major; out (ncomp, n, n), n = nstates + with_ground.
+   All pointers of one ptr_kind. */
+int xt_tdm_sc(const xt_tdm_sc_desc* desc, const double* op_ao, const double* c_occ_a, const double* c_vir_a,
+              const double* c_occ_b, const double* c_vir_b, const double* vecs, double* out, int ptr_kind,
+              void* hip_stream);
+
 /* mean-field front end ------------------------------ */
 /* 3-index Coulomb integrals (ab|c) over contracted Cartesian Gaussians by
    McMurchie-Davidson (replaces libcint int3c2e behind PySCF df.incore.aux_e2,

@@ -30,7 +30,7 @@ EXPORTS = [
     "xt_set_grid", "xt_set_oo_basis", "xt_apply", "xt_dim", "xt_last_timings",
     "xt_xsf_j_diagonals", "xt_set_exchange_mode", "xt_prepare", "xt_exchange_plan", "xt_set_partition", "xt_set_profile",
     "xt_profile_stats", "xt_profile_bytes", "xt_dgemm", "xt_dgemm_strided", "xt_precond", "xt_row_norms2", "xt_row_scale", "xt_build_id",
-    "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao", "xt_tdm",
+    "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao", "xt_tdm", "xt_tdm_sc",
 ]
 
 
@@ -54,7 +54,15 @@ class XtTdmDesc(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 7   # include/xtddft_amd.h XT_ABI_VERSION
+class XtTdmScDesc(ctypes.Structure):
+    _fields_ = [
+        ("nao", c_int), ("nocc_a", c_int), ("nvir_a", c_int), ("nocc_b", c_int), ("nvir_b", c_int),
+        ("ncomp", c_int), ("nstates", c_int), ("spin_adapted", c_int), ("no", c_int), ("si", c_double),
+        ("with_ground", c_int),
+    ]
+
+
+ABI_VERSION = 7  # include/xtddft_amd.h XT_ABI_VERSION
 
 
 class LibraryMissing(RuntimeError):
@@ -120,6 +128,7 @@ def lib():
                                 c_int, dp, c_long, vp]
     L.xt_eval_ao.argtypes = [c_int, dp, c_int, vp, dp, dp, dp, c_int, dp, c_long, c_long, vp]
     L.xt_tdm.argtypes = [POINTER(XtTdmDesc), dp, dp, dp, dp, dp, dp, c_int, vp]
+    L.xt_tdm_sc.argtypes = [POINTER(XtTdmScDesc), dp, dp, dp, dp, dp, dp, dp, c_int, vp]
     for name in EXPORTS:
         if not hasattr(L, name):
             raise LibraryMissing(f"{LIB_PATH} lacks symbol {name}")

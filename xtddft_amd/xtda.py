@@ -218,6 +218,59 @@ class XTDA:
         vt = self.v.T
         return np.einsum('xi,yi->yx', a, vt[:, :na]) + np.einsum('xi,yi->yx', b, vt[:, na:])
 
+    # ---- moments between roots on the device (xt_tdm_sc) ----
+    def transition_dipoles(self, op_ao=None, ground=True):
+        """(ncomp, n+1, n+1) moments between the solved roots with the reference state as
+        row / column 0, or (ncomp, n, n) without it (``ground=False``): TDM_S / TDM_GSS of
+        x2c_hamiltonian/driver/tdm.py:6-126 as X_TDA.calculate_TDM calls them
+        (XTDA.py:1354-1400), for ROKS (spin-adapted, S = no/2) and UKS (spin-orbital) alike.
+        ``op_ao`` (ncomp, nao, nao) symmetric defaults to ``int1e_r`` at the centre of nuclear
+        charge (XTDA.py:1355-1362).  In the phase of ``utils.so2st`` the couplings of CV(1)
+        with CO(0) and OV(0) carry -sqrt((S+1)/(2S)); tdm.py writes + for a CV(1) of the
+        opposite sign."""
+        from . import tdm as _tdm
+        if op_ao is None:
+            op_ao = _tdm.charge_centre_dipole(self.mf, self.mol)
+        inv = np.empty_like(self.order)
+        inv[self.order] = np.arange(self.order.size)
+        vecs = np.ascontiguousarray(self.v[inv, :].T)    # "my order" -> PySCF order [za | zb]
+        coa, cva, cob, cvb = self._spin_orbitals()
+        return _tdm.transition_moments_sc(op_ao, coa, cva, cob, cvb, vecs, spin_adapted=self.X, no=self.no,
+                                          si=self.no / 2, ground=ground, device=self.device)
+
+    def _state_energies(self):
+        return np.concatenate([[0.0], np.asarray(self.e)[:self.v.shape[1]]])
+
+    def osc_matrix(self, op_ao=None):
+        """(n+1, n+1) oscillator strengths (2/3)|E_i - E_j| sum_x T_x[i,j]^2 with energies
+        [0, e_1..e_n] (XTDA.py:1379, 1398): row 0 is ground -> excited absorption, the rest
+        excited-state absorption."""
+        from . import tdm as _tdm
+        t = self.transition_dipoles(op_ao)
+        return _tdm.osc_matrix(self._state_energies(), t)
+
+    def state_dipoles(self, op_ao=None, reference=None):
+        """(n, ncomp) moments of the excited states: the diagonal of T (the change against the
+        reference state) plus ``reference``, the reference state's own moment (electronic +
+        nuclear, XTDA.py:1364-1368, 1397), when given."""
+        t = self.transition_dipoles(op_ao, ground=False)
+        dip = np.einsum('xii->ix', t)
+        return dip if reference is None else dip + np.asarray(reference, dtype=np.float64)[None, :]
+
+    def calculate_TDM(self, verbose=True):
+        """X_TDA.calculate_TDM (XTDA.py:1354-1400): returns ``(tdm, osc)`` = the dipole
+        ``transition_dipoles()`` and its ``osc_matrix`` and prints the reference's two tables,
+        ground <-> excited and every ordered pair of excited states.  The diagonal lines hold
+        the moment's change against the reference state (``state_dipoles`` adds the
+        reference's own moment)."""
+        from . import tdm as _tdm
+        t = self.transition_dipoles()
+        e = self._state_energies()
+        osc = _tdm.osc_matrix(e, t)
+        if verbose:
+            print("\n".join(_tdm.tdm_tables_sc(e[1:], t)))
+        return t, osc
+
     def _qc_mol(self):
         mol = self.mol if hasattr(self.mol, "intor") else self.mf.extra.get("qc_mol")
         if mol is None or not hasattr(mol, "intor"):
