@@ -15,7 +15,7 @@
 extern "C" {
 #endif
 
-#define XT_ABI_VERSION 7
+#define XT_ABI_VERSION 8
 
 #define XT_PTR_HOST 0
 #define XT_PTR_DEVICE 1
@@ -197,11 +197,42 @@ int xt_dgemm_strided(int m, int n, int k, int r, int nbatch, double alpha,
                      const double* a, long sAm, long sAk, long sAr, long sAb,
                      const double* b, long sBk, long sBn, long sBr, long sBb, double beta,
                      double* c, long ldc, long sCb, void* hip_stream);
+/* The engine behind xt_dgemm with every field of its contraction exposed, so that each tile
+   configuration, staging path and layout it can launch is reachable from a test:
+     C[b1,b2](m, n) = alpha sum_{r' < r} sum_{k' < k} A(b, r', m, k') B(b, r', k', n) + beta C[b1,b2](m, n)
+     A(b, r', m, k') = a[b1 sAb1 + b2 sAb2 + r' sAr + m sAm + k' sAk]      (sAm or sAk = 1)
+     B(b, r', k', n) = b[b1 sBb1 + b2 sBb2 + r' sBr + k' sBk + n sBn]      (sBk or sBn = 1)
+     C[b1,b2](m, n)  = c[b1 sCb1 + b2 sCb2 + m ldc + n]
+   rdiv > 0 (A m-contiguous only; the stored-exchange build's rows): row m = (hi, lo) =
+   (m / rdiv, m % rdiv) sits at hi sAm_hi + lo in A and at hi sC_hi + lo ldc in C.
+   max_split > 0 caps the split-K count; tag 0..5 selects a call site's kernel symbol and
+   planning rule and must come with that site's layout (1, 4: A k-contiguous and B
+   n-contiguous; 2: both k-contiguous; 3, 5: A m-contiguous and B n-contiguous).  Strides are
+   >= 0 (0 broadcasts an operand over a batch index). */
+typedef struct xt_gemm_desc {
+  int m, n, k, r, nb1, nb2;
+  double alpha, beta;
+  long sAm, sAk, sAr, sAb1, sAb2;
+  long sBk, sBn, sBr, sBb1, sBb2;
+  long ldc, sCb1, sCb2;
+  int rdiv; long sAm_hi, sC_hi;
+  int max_split, tag;
+  long ws_bytes;            /* split-K workspace cap; 0 = the default 256 MiB */
+} xt_gemm_desc;
+/* What xt_gemm_run would launch for this descriptor -- host only, no HIP call: the tile
+   configuration (index, bm x bn tile, bk-deep K tiles), the split-K count after the
+   workspace cap, and whether every K tile takes the masked staging (r > 1 and k % bk != 0).
+   m = 0 or n = 0 launches nothing: cfg = -1, the rest 0. */
+int xt_gemm_plan(const xt_gemm_desc* desc, int* cfg, int* bm, int* bn, int* bk, int* nsplit, int* masked);
+/* Runs the contraction (plain mode, device pointers) on hip_stream.  The descriptor is
+   validated before any HIP call. */
+int xt_gemm_run(const xt_gemm_desc* desc, const double* a, const double* b, double* c, void* hip_stream);
 /* y = (x - e*w) / clamp(d - (e - shift)) row-wise; diag preconditioner
    (XTDA.py:736-744, PySCF make_diag_precond). nrow vectors of length dim. */
 int xt_precond(int nrow, int dim, const double* diag, const double* e, double shift,
                const double* r, double* out, void* hip_stream);
-/* out[i] = sum_j x[i,j]^2 for nrow rows. */
+/* out[i] = sum_j x[i,j]^2 for nrow rows.  This and its two neighbours reject negative sizes
+   and, where there is work, null pointers; nrow = 0 or dim = 0 returns 0 and touches nothing. */
 int xt_row_norms2(int nrow, int dim, const double* x, double* out, void* hip_stream);
 /* x[i,:] *= s[i] */
 int xt_row_scale(int nrow, int dim, double* x, const double* s, void* hip_stream);

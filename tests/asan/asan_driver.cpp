@@ -63,6 +63,55 @@ int main() {
              "dgemm_strided null A");
   expect_err(xt_dgemm_strided(4, 4, 4, 2, 1, 1.0, buf, 4, 1, -16, 0, buf, 4, 1, 16, 0, 0.0, buf, 4, 0, nullptr),
              "dgemm_strided negative stride");
+  expect_err(xt_dgemm(0, 0, -1, 4, 4, 1.0, buf, 4, buf, 4, 0.0, buf, 4, nullptr), "dgemm negative m");
+  expect_err(xt_dgemm(0, 0, 2, 2, 4, 1.0, buf, 3, buf, 2, 0.0, buf, 2, nullptr), "dgemm lda < k");
+  expect_err(xt_dgemm(1, 0, 2, 2, 2, 1.0, buf, 1, buf, 2, 0.0, buf, 2, nullptr), "dgemm lda < m (transposed)");
+  expect_err(xt_dgemm(0, 0, 2, 2, 2, 1.0, buf, 2, buf, 1, 0.0, buf, 2, nullptr), "dgemm ldb < n");
+  expect_err(xt_dgemm(0, 1, 2, 2, 4, 1.0, buf, 4, buf, 3, 0.0, buf, 2, nullptr), "dgemm ldb < k (transposed)");
+  expect_err(xt_dgemm(0, 0, 2, 2, 2, 1.0, buf, 2, buf, 2, 0.0, buf, 1, nullptr), "dgemm ldc < n");
+  expect_err(xt_dgemm(0, 0, 2, 2, 2, 1.0, nullptr, 2, buf, 2, 0.0, buf, 2, nullptr), "dgemm null A");
+  expect_err(xt_dgemm(0, 0, 2, 2, 0, 1.0, nullptr, 2, nullptr, 2, 0.0, nullptr, 2, nullptr), "dgemm null C");
+  if (xt_dgemm(0, 0, 0, 2, 2, 1.0, nullptr, 2, nullptr, 2, 0.0, nullptr, 2, nullptr) != 0) {
+    std::printf("FAIL dgemm m = 0 is a no-op\n"); ++failures;
+  }
+  expect_err(xt_precond(-1, 2, buf, buf, 0.0, buf, buf, nullptr), "precond negative nrow");
+  expect_err(xt_precond(2, 2, buf, nullptr, 0.0, buf, buf, nullptr), "precond null e");
+  expect_err(xt_precond(2, 2, buf, buf, 0.0, buf, nullptr, nullptr), "precond null out");
+  expect_err(xt_row_norms2(2, -2, buf, buf, nullptr), "row_norms2 negative dim");
+  expect_err(xt_row_norms2(2, 2, nullptr, buf, nullptr), "row_norms2 null x");
+  expect_err(xt_row_scale(-2, 2, buf, buf, nullptr), "row_scale negative nrow");
+  expect_err(xt_row_scale(2, 2, buf, nullptr, nullptr), "row_scale null s");
+  buf[0] = 3.0;
+  if (xt_precond(0, 2, buf, buf, 0.0, buf, buf, nullptr) != 0 || xt_row_norms2(2, 0, buf, buf, nullptr) != 0 ||
+      xt_row_scale(0, 0, buf, buf, nullptr) != 0 || buf[0] != 3.0) {
+    std::printf("FAIL zero-size helper calls are no-ops\n"); ++failures;
+  }
+  buf[0] = 0.0;
+  {
+    xt_gemm_desc g;
+    std::memset(&g, 0, sizeof(g));
+    int o[6];
+    g.m = 4; g.n = 4; g.k = 4; g.r = 1; g.nb1 = 1; g.nb2 = 1; g.alpha = 1.0;
+    g.sAm = 4; g.sAk = 1; g.sBk = 4; g.sBn = 1; g.ldc = 4;
+    if (xt_gemm_plan(&g, o, o + 1, o + 2, o + 3, o + 4, o + 5) != 0 || o[0] != 4 || o[1] != 64 || o[4] != 1) {
+      std::printf("FAIL gemm_plan of a valid descriptor\n"); ++failures;
+    }
+    expect_err(xt_gemm_plan(nullptr, o, o + 1, o + 2, o + 3, o + 4, o + 5), "gemm_plan null desc");
+    expect_err(xt_gemm_plan(&g, nullptr, o + 1, o + 2, o + 3, o + 4, o + 5), "gemm_plan null output");
+    expect_err(xt_gemm_run(&g, nullptr, buf, buf, nullptr), "gemm_run null A");
+    g.ldc = 3;
+    expect_err(xt_gemm_run(&g, buf, buf, buf, nullptr), "gemm_run ldc < n");
+    g.ldc = 4; g.sAk = 2;
+    expect_err(xt_gemm_plan(&g, o, o + 1, o + 2, o + 3, o + 4, o + 5), "gemm_plan A without a unit stride");
+    g.sAk = 1; g.tag = 3;
+    expect_err(xt_gemm_run(&g, buf, buf, buf, nullptr), "gemm_run tag 3 on (k, n) operands");
+    g.tag = 0; g.rdiv = 2;
+    expect_err(xt_gemm_plan(&g, o, o + 1, o + 2, o + 3, o + 4, o + 5), "gemm_plan rdiv with A k-contiguous");
+    g.rdiv = 0; g.sBb2 = -1;
+    expect_err(xt_gemm_run(&g, buf, buf, buf, nullptr), "gemm_run negative stride");
+    g.sBb2 = 0; g.r = 0;
+    expect_err(xt_gemm_plan(&g, o, o + 1, o + 2, o + 3, o + 4, o + 5), "gemm_plan r < 1");
+  }
   expect_err(xt_int2e_cart(-1, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0.0, nullptr,
                            nullptr, 0.0, 0, nullptr, 0, nullptr), "int2e negative npair");
   expect_err(xt_int2e_cart(1, nullptr, nullptr, nullptr, 1, nullptr, nullptr, nullptr, 4, 0, 0.0, nullptr,

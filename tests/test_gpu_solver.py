@@ -67,6 +67,100 @@ def test_dgemm_strided_reduce_index(torch, hiplib, m, n, k, r, nb, ak, bk):
     assert float((c - ref).abs().max()) / scale < 1e-13 * (r * k) ** 0.5
 
 
+# ---- Davidson helper kernels (xt_kernels.hip: k_precond, k_row_norms2, k_row_scale) --------
+# dim around the 256-thread block, one dim far past it, one and several rows, and 70000 rows
+# (more row blocks than the 65536-block cap of the element-wise launches)
+HELPER_SIZES = [(nrow, dim) for dim in (1, 255, 256, 257, 100003) for nrow in (1, 3)] + [(70000, 5)]
+# more than 65536 x 256 elements: the second lap of the grid-stride loop
+HELPER_SIZES_ELEMENTWISE = HELPER_SIZES + [(3, 6000001)]
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.int64), np.ascontiguousarray(b).view(np.int64))
+
+
+@pytest.mark.parametrize("nrow,dim", HELPER_SIZES_ELEMENTWISE)
+def test_precond_matches_numpy_bitwise(torch, hiplib, nrow, dim):
+    """xt_precond against r / where(|d| < 1e-8, 1e-8, d), d = diag - (e - shift) in that
+    order, with a different e per row and entries of row 0 at d = +3e-9, -3e-9 and exactly 0
+    (all three clamp to +1e-8).  One subtraction pair and one IEEE division per element, no
+    fast-math: bit-identical."""
+    from xtddft_amd import _capi
+    rng = np.random.default_rng(nrow * 1000003 + dim)
+    shift = 0.1
+    e = 0.3 + 0.05 * np.arange(nrow) + 0.01 * rng.random(nrow)
+    diag = 0.5 + 1.5 * rng.random(dim)
+    t0 = e[0] - shift
+    special = [(dim // 2, t0), (dim // 3, t0 + 3e-9), (dim - 1, t0 - 3e-9)][:min(3, dim)]
+    for j, v in special:
+        diag[j] = v
+    r = rng.standard_normal((nrow, dim))
+    d = diag[None, :] - (e[:, None] - shift)
+    small = np.abs(d) < 1e-8
+    assert small[0].sum() == len({j for j, _ in special}) and (d[0, dim // 2] == 0.0)
+    if dim >= 3:
+        assert d[0, dim // 3] > 0 and d[0, dim - 1] < 0
+    ref = r / np.where(small, 1e-8, d)
+    dd, de, dr = (torch.from_numpy(x).cuda() for x in (diag, e, r))
+    out = torch.full_like(dr, float("nan"))
+    st = torch.cuda.current_stream().cuda_stream
+    _capi.check(hiplib.xt_precond(nrow, dim, dd.data_ptr(), de.data_ptr(), shift, dr.data_ptr(), out.data_ptr(),
+                                  ctypes.c_void_p(st)), "xt_precond")
+    torch.cuda.synchronize()
+    assert _same_bits(out.cpu().numpy(), ref)
+
+
+@pytest.mark.parametrize("nrow,dim", HELPER_SIZES_ELEMENTWISE)
+def test_row_scale_matches_numpy_bitwise(torch, hiplib, nrow, dim):
+    from xtddft_amd import _capi
+    rng = np.random.default_rng(nrow * 1000003 + dim + 1)
+    x = rng.standard_normal((nrow, dim))
+    s = rng.standard_normal(nrow)
+    dx, ds = torch.from_numpy(x).cuda(), torch.from_numpy(s).cuda()
+    st = torch.cuda.current_stream().cuda_stream
+    _capi.check(hiplib.xt_row_scale(nrow, dim, dx.data_ptr(), ds.data_ptr(), ctypes.c_void_p(st)), "xt_row_scale")
+    torch.cuda.synchronize()
+    assert _same_bits(dx.cpu().numpy(), x * s[:, None])
+
+
+@pytest.mark.parametrize("nrow,dim", HELPER_SIZES)
+def test_row_norms2_within_the_derived_bound(torch, hiplib, nrow, dim):
+    """xt_row_norms2 against math.fsum of the squares.  Each of the 256 threads sums
+    ceil(dim / 256) squares (one rounding per square and per addition, or one per fused
+    multiply-add), then an 8-level tree adds the partial sums: every term passes through at
+    most ceil(dim / 256) + 9 roundings, and all terms are positive, so the relative error is
+    at most (ceil(dim / 256) + 9) 2^-53."""
+    import math
+    from xtddft_amd import _capi
+    rng = np.random.default_rng(nrow * 1000003 + dim + 2)
+    x = rng.standard_normal((nrow, dim))
+    dx = torch.from_numpy(x).cuda()
+    out = torch.full((nrow,), float("nan"), dtype=torch.float64, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    _capi.check(hiplib.xt_row_norms2(nrow, dim, dx.data_ptr(), out.data_ptr(), ctypes.c_void_p(st)), "xt_row_norms2")
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    sq = x * x
+    ref = np.array([math.fsum(row) for row in sq])
+    bound = (-(-dim // 256) + 9) * 2.0 ** -53
+    rel = np.abs(got - ref) / ref
+    print(f"row_norms2 {nrow} x {dim}: max relative error {rel.max():.3e}, bound {bound:.3e}")
+    assert (rel <= bound).all()
+
+
+def test_helper_kernels_zero_sizes_touch_nothing(torch, hiplib):
+    """nrow == 0 or dim == 0: return 0, launch nothing, leave the outputs alone."""
+    x = torch.full((4,), 7.0, dtype=torch.float64, device="cuda")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = x.data_ptr()
+    for nrow, dim in ((0, 4), (4, 0), (0, 0)):
+        assert hiplib.xt_precond(nrow, dim, p, p, 0.0, p, p, st) == 0
+        assert hiplib.xt_row_norms2(nrow, dim, p, p, st) == 0
+        assert hiplib.xt_row_scale(nrow, dim, p, p, st) == 0
+    torch.cuda.synchronize()
+    assert bool((x == 7.0).all())
+
+
 def test_davidson_checkpoint_and_restart(torch, tmp_path):
     """davidson.checkpoint saves the Ritz vectors every iteration; a solve restarted from
     the file (x0 = restart_guess) converges to the same roots in fewer iterations."""

@@ -28,7 +28,7 @@ def test_library_builds_and_exports_every_header_symbol(hiplib):
     for s in syms:
         assert hasattr(hiplib, s), s
     from xtddft_amd._capi import ABI_VERSION
-    assert hiplib.xt_abi_version() == ABI_VERSION == 7
+    assert hiplib.xt_abi_version() == ABI_VERSION == 8
 
 
 def test_desc_layout_matches_c_header(tmp_path):
@@ -44,6 +44,109 @@ def test_desc_layout_matches_c_header(tmp_path):
     out = [int(v) for v in subprocess.check_output([str(exe)]).split()]
     assert out[0] == ctypes.sizeof(XtDesc)
     assert out[1:] == [getattr(XtDesc, f).offset for f in fields]
+
+
+def test_gemm_desc_layout_matches_c_header(tmp_path):
+    """ctypes XtGemmDesc has the same size/offsets as the C struct xt_gemm_desc."""
+    from xtddft_amd._capi import XtGemmDesc
+    fields = [f for f, _ in XtGemmDesc._fields_]
+    src = tmp_path / "t.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "xtddft_amd.h"\nint main(){'
+                   'printf("%zu", sizeof(xt_gemm_desc));' +
+                   "".join(f'printf(" %zu", offsetof(xt_gemm_desc, {f}));' for f in fields) + "return 0;}")
+    exe = tmp_path / "t"
+    subprocess.check_call(["gcc", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)])
+    out = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    assert out[0] == ctypes.sizeof(XtGemmDesc)
+    assert out[1:] == [getattr(XtGemmDesc, f).offset for f in fields]
+    # every field of the C struct is bound, in order
+    txt = open(HEADER).read()
+    body = re.search(r"typedef struct xt_gemm_desc \{(.*?)\} xt_gemm_desc;", txt, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n for decl in body.split(";") for n in re.findall(r"(\w+)\s*(?:,|$)", re.sub(r"^\s*(int|long|double)\s", "", decl.strip()))]
+    assert names == fields
+
+
+def test_device_linear_algebra_rejects_bad_arguments_without_gpu(hiplib):
+    """xt_dgemm, xt_precond, xt_row_norms2, xt_row_scale, xt_gemm_plan and xt_gemm_run check
+    their arguments before the first HIP call: on a machine without a GPU every rejected call
+    returns XT_ERR_ARG (-1) with its own message -- not XT_ERR_HIP (-3) from a failed HIP call."""
+    from xtddft_amd import _capi
+    buf = np.zeros(64)
+    p = buf.ctypes.data
+    L = hiplib
+
+    def rejected(rc, word):
+        assert rc == -1, rc
+        assert word.encode() in L.xt_last_error(), L.xt_last_error()
+
+    # xt_dgemm(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, stream)
+    rejected(L.xt_dgemm(0, 0, -1, 4, 4, 1.0, p, 4, p, 4, 0.0, p, 4, None), "negative")
+    rejected(L.xt_dgemm(0, 0, 4, -1, 4, 1.0, p, 4, p, 4, 0.0, p, 4, None), "negative")
+    rejected(L.xt_dgemm(0, 0, 4, 4, -1, 1.0, p, 4, p, 4, 0.0, p, 4, None), "negative")
+    rejected(L.xt_dgemm(0, 0, 4, 5, 6, 1.0, p, 5, p, 5, 0.0, p, 5, None), "lda")     # A rows hold k = 6
+    rejected(L.xt_dgemm(1, 0, 4, 5, 6, 1.0, p, 3, p, 5, 0.0, p, 5, None), "lda")     # A^T rows hold m = 4
+    rejected(L.xt_dgemm(0, 0, 4, 5, 6, 1.0, p, 6, p, 4, 0.0, p, 5, None), "ldb")     # B rows hold n = 5
+    rejected(L.xt_dgemm(0, 1, 4, 5, 6, 1.0, p, 6, p, 5, 0.0, p, 5, None), "ldb")     # B^T rows hold k = 6
+    rejected(L.xt_dgemm(0, 0, 4, 5, 6, 1.0, p, 6, p, 5, 0.0, p, 4, None), "ldc")
+    rejected(L.xt_dgemm(0, 0, 4, 5, 6, 1.0, None, 6, p, 5, 0.0, p, 5, None), "null")
+    rejected(L.xt_dgemm(0, 0, 4, 5, 6, 1.0, p, 6, None, 5, 0.0, p, 5, None), "null")
+    rejected(L.xt_dgemm(0, 0, 4, 5, 6, 1.0, p, 6, p, 5, 0.0, None, 5, None), "null")
+    rejected(L.xt_dgemm(0, 0, 4, 5, 0, 1.0, None, 1, None, 5, 0.0, None, 5, None), "null")   # C = beta C needs C
+    # nothing to do: accepted with null operands, still without a HIP call
+    assert L.xt_dgemm(0, 0, 0, 5, 6, 1.0, None, 6, None, 5, 0.0, None, 5, None) == 0
+    assert L.xt_dgemm(1, 1, 4, 0, 6, 1.0, None, 4, None, 6, 0.0, None, 1, None) == 0
+
+    rejected(L.xt_precond(-1, 4, p, p, 0.0, p, p, None), "negative")
+    rejected(L.xt_precond(2, -4, p, p, 0.0, p, p, None), "negative")
+    for k in range(4):
+        args = [p, p, 0.0, p, p]
+        args[k if k < 2 else k + 1] = None
+        rejected(L.xt_precond(2, 4, *args, None), "null")
+    rejected(L.xt_row_norms2(-1, 4, p, p, None), "negative")
+    rejected(L.xt_row_norms2(2, -1, p, p, None), "negative")
+    rejected(L.xt_row_norms2(2, 4, None, p, None), "null")
+    rejected(L.xt_row_norms2(2, 4, p, None, None), "null")
+    rejected(L.xt_row_scale(-1, 4, p, p, None), "negative")
+    rejected(L.xt_row_scale(2, -1, p, p, None), "negative")
+    rejected(L.xt_row_scale(2, 4, None, p, None), "null")
+    rejected(L.xt_row_scale(2, 4, p, None, None), "null")
+    # nrow == 0 or dim == 0: nothing to do, nothing touched (host memory here: a launch would fault)
+    buf[:] = 5.0
+    for nrow, dim in ((0, 4), (4, 0)):
+        assert L.xt_precond(nrow, dim, p, p, 0.0, p, p, None) == 0
+        assert L.xt_row_norms2(nrow, dim, p, p, None) == 0
+        assert L.xt_row_scale(nrow, dim, p, p, None) == 0
+    assert (buf == 5.0).all()
+
+    def desc(**kw):
+        d = _capi.XtGemmDesc(m=4, n=5, k=6, r=1, nb1=1, nb2=1, alpha=1.0, beta=0.0, sAm=6, sAk=1, sBk=5, sBn=1, ldc=5)
+        for name, v in kw.items():
+            setattr(d, name, v)
+        return d
+
+    outs = [ctypes.c_int() for _ in range(6)]
+    refs = [ctypes.byref(o) for o in outs]
+    assert L.xt_gemm_plan(ctypes.byref(desc()), *refs) == 0 and outs[0].value == 4
+    bad = [(dict(m=-1), "sizes"), (dict(r=0), "sizes"), (dict(nb2=0), "sizes"), (dict(nb1=70000), "batches"),
+           (dict(sAm=6, sAk=2), "unit"), (dict(sBk=5, sBn=2), "unit"), (dict(sAr=-1), "negative stride"),
+           (dict(sCb2=-8), "negative stride"), (dict(ldc=4), "ldc"), (dict(rdiv=-1), "rdiv"),
+           (dict(rdiv=2), "rdiv"),                               # A k-contiguous
+           (dict(max_split=-1), "negative"), (dict(ws_bytes=-1), "negative"), (dict(tag=6), "tag"), (dict(tag=-1), "tag"),
+           (dict(tag=2), "tag"), (dict(tag=3), "tag"),           # (k, n) operands: tags 1 and 4 only
+           (dict(sAm=1 << 40, sAk=1), "addressable")]
+    for kw, word in bad:
+        rejected(L.xt_gemm_plan(ctypes.byref(desc(**kw)), *refs), word)
+        rejected(L.xt_gemm_run(ctypes.byref(desc(**kw)), p, p, p, None), word)
+    assert L.xt_gemm_plan(ctypes.byref(desc(tag=1)), *refs) == 0
+    assert L.xt_gemm_plan(ctypes.byref(desc(tag=4)), *refs) == 0
+    rejected(L.xt_gemm_plan(None, *refs), "null")
+    rejected(L.xt_gemm_plan(ctypes.byref(desc()), None, *refs[1:]), "null")
+    rejected(L.xt_gemm_run(None, p, p, p, None), "null")
+    rejected(L.xt_gemm_run(ctypes.byref(desc()), None, p, p, None), "null")
+    rejected(L.xt_gemm_run(ctypes.byref(desc()), p, None, p, None), "null")
+    rejected(L.xt_gemm_run(ctypes.byref(desc()), p, p, None, None), "null")
+    assert L.xt_gemm_run(ctypes.byref(desc(m=0)), None, None, None, None) == 0
 
 
 def test_create_rejects_bad_descriptor_without_gpu(hiplib):

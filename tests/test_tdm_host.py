@@ -64,7 +64,7 @@ def test_restatement_block_rows_roundtrip():
 def test_header_declares_and_library_exports_xt_tdm(hiplib):
     txt = open(HEADER).read()
     assert re.search(r"^\s*int\s+xt_tdm\s*\(", txt, re.M)
-    assert "XT_ABI_VERSION 7" in txt
+    assert "XT_ABI_VERSION 8" in txt
     assert hasattr(hiplib, "xt_tdm")
     from xtddft_amd import _capi, build
     assert "xt_tdm" in _capi.EXPORTS and "xt_tdm.hip" in build.SOURCES

@@ -100,7 +100,7 @@ def test_ground_row_equals_the_contraction_of_xtda_transition(shape):
 def test_header_declares_and_library_exports_xt_tdm_sc(hiplib):
     txt = open(HEADER).read()
     assert re.search(r"^\s*int\s+xt_tdm_sc\s*\(", txt, re.M)
-    assert "XT_ABI_VERSION 7" in txt
+    assert "XT_ABI_VERSION 8" in txt
     assert hasattr(hiplib, "xt_tdm_sc")
     from xtddft_amd import _capi, build
     assert "xt_tdm_sc" in _capi.EXPORTS and "xt_tdm_sc.hip" in build.SOURCES

@@ -30,7 +30,7 @@ EXPORTS = [
     "xt_set_grid", "xt_set_oo_basis", "xt_apply", "xt_dim", "xt_last_timings",
     "xt_xsf_j_diagonals", "xt_set_exchange_mode", "xt_prepare", "xt_exchange_plan", "xt_set_partition", "xt_set_profile",
     "xt_profile_stats", "xt_profile_bytes", "xt_dgemm", "xt_dgemm_strided", "xt_precond", "xt_row_norms2", "xt_row_scale", "xt_build_id",
-    "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao", "xt_tdm", "xt_tdm_sc",
+    "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao", "xt_tdm", "xt_tdm_sc", "xt_gemm_plan", "xt_gemm_run",
 ]
 
 
@@ -62,7 +62,20 @@ class XtTdmScDesc(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 7  # include/xtddft_amd.h XT_ABI_VERSION
+class XtGemmDesc(ctypes.Structure):
+    """xt_gemm_desc: every field of the engine's contraction (xt_gemm_plan / xt_gemm_run)."""
+    _fields_ = [
+        ("m", c_int), ("n", c_int), ("k", c_int), ("r", c_int), ("nb1", c_int), ("nb2", c_int),
+        ("alpha", c_double), ("beta", c_double),
+        ("sAm", c_long), ("sAk", c_long), ("sAr", c_long), ("sAb1", c_long), ("sAb2", c_long),
+        ("sBk", c_long), ("sBn", c_long), ("sBr", c_long), ("sBb1", c_long), ("sBb2", c_long),
+        ("ldc", c_long), ("sCb1", c_long), ("sCb2", c_long),
+        ("rdiv", c_int), ("sAm_hi", c_long), ("sC_hi", c_long),
+        ("max_split", c_int), ("tag", c_int), ("ws_bytes", c_long),
+    ]
+
+
+ABI_VERSION = 8  # include/xtddft_amd.h XT_ABI_VERSION
 
 
 class LibraryMissing(RuntimeError):
@@ -129,6 +142,9 @@ def lib():
     L.xt_eval_ao.argtypes = [c_int, dp, c_int, vp, dp, dp, dp, c_int, dp, c_long, c_long, vp]
     L.xt_tdm.argtypes = [POINTER(XtTdmDesc), dp, dp, dp, dp, dp, dp, c_int, vp]
     L.xt_tdm_sc.argtypes = [POINTER(XtTdmScDesc), dp, dp, dp, dp, dp, dp, dp, c_int, vp]
+    pi = POINTER(c_int)
+    L.xt_gemm_plan.argtypes = [POINTER(XtGemmDesc), pi, pi, pi, pi, pi, pi]
+    L.xt_gemm_run.argtypes = [POINTER(XtGemmDesc), dp, dp, dp, vp]
     for name in EXPORTS:
         if not hasattr(L, name):
             raise LibraryMissing(f"{LIB_PATH} lacks symbol {name}")

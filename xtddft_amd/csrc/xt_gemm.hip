@@ -880,8 +880,13 @@ void plan_gemm(const GemmDesc& d, GemmParams* pp, int* cfg_out) {
   *cfg_out = cfg;
 }
 
-int dgemm(const GemmDesc& d, hipStream_t st, double* ws, size_t ws_bytes) {
-  if (d.M <= 0 || d.N <= 0) return 0;
+void gemm_cfg_tile(int cfg, int* bm, int* bn, int* bk) {
+  const Cfg& c = kCfg[cfg];
+  *bm = c.bm; *bn = c.bn; *bk = c.bk;
+}
+
+// The layout and addressing rules of dgemm(), host only (no HIP call): 0 or XT_ERR_ARG.
+int dgemm_check(const GemmDesc& d) {
   const int mode = d.fz.mode;
   if (mode != 0 && (d.sAm != 1 || d.fz.w == nullptr || d.fz.rho == nullptr || d.fz.nx <= 0 || d.fz.V <= 0))
     return XT_ERR_ARG;
@@ -899,6 +904,27 @@ int dgemm(const GemmDesc& d, hipStream_t st, double* ws, size_t ws_bytes) {
   // two-level rows: the whole row range sits in one 2 GB buffer window off the batch origin
   if (d.rdiv > 0 && (((long)(d.M / d.rdiv) * d.sAm_hi + d.rdiv + 32L * d.sAk) * 8 >= (1L << 31))) return XT_ERR_ARG;
   if ((bkc ? (256L * d.sBn + 32) : (32L * d.sBk + 256L)) * 8 >= lim) return XT_ERR_ARG;
+  return 0;
+}
+
+// The split count dgemm() launches for a planned one, given the workspace it is handed.
+int dgemm_fit_split(const GemmParams& p, bool have_ws, size_t ws_bytes) {
+  if (p.nsplit <= 1) return p.nsplit;
+  const size_t need = sizeof(double) * (size_t)p.nsplit * p.nbatch * (size_t)p.M * p.N;
+  if (have_ws && ws_bytes >= need) return p.nsplit;
+  // fall back to fewer splits that fit the workspace
+  const long per = sizeof(double) * (long)p.nbatch * p.M * p.N;
+  const long s = have_ws ? (long)(ws_bytes / per) : 0;
+  const int nsplit = s >= 2 ? (int)s : 1;
+  return nsplit > 64 ? 64 : nsplit;
+}
+
+int dgemm(const GemmDesc& d, hipStream_t st, double* ws, size_t ws_bytes) {
+  if (d.M <= 0 || d.N <= 0) return 0;
+  if (dgemm_check(d)) return XT_ERR_ARG;
+  const int mode = d.fz.mode;
+  const bool akc = mode == 0 && (d.sAk == 1);
+  const bool bkc = mode != 0 || (d.sBk == 1);
   GemmParams p; int cfg;
   plan_gemm(d, &p, &cfg);
   if (d.K <= 0) {   // C = beta*C
@@ -906,14 +932,7 @@ int dgemm(const GemmDesc& d, hipStream_t st, double* ws, size_t ws_bytes) {
     p.R = 1; p.K = 0;
   }
   if (p.nsplit > 1) {
-    size_t need = sizeof(double) * (size_t)p.nsplit * p.nbatch * (size_t)p.M * p.N;
-    if (ws == nullptr || ws_bytes < need) {
-      // fall back to fewer splits that fit the workspace
-      long per = sizeof(double) * (long)p.nbatch * p.M * p.N;
-      long s = ws ? (long)(ws_bytes / per) : 0;
-      p.nsplit = s >= 2 ? (int)s : 1;
-      if (p.nsplit > 64) p.nsplit = 64;
-    }
+    p.nsplit = dgemm_fit_split(p, ws != nullptr, ws_bytes);
     p.ws = ws;
   }
   if (mode == 1) {

@@ -173,6 +173,12 @@ int eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info, 
 int xc_rho_w(int O, int nx, int V, int n, const double* PO, long ldp, const double* Z, long zi, long zx,
              const double* W, long wc, long wg, double* R, long rg, hipStream_t st);
 size_t dgemm_workspace_bytes(const GemmDesc& d);
+// host only: dgemm()'s layout / addressing checks (0 or XT_ERR_ARG), and the split count it
+// launches for a planned one when handed ws_bytes of workspace (fewer splits when the slabs
+// do not fit)
+int dgemm_check(const GemmDesc& d);
+void gemm_cfg_tile(int cfg, int* bm, int* bn, int* bk);   // tile of a plain-mode cfg (plan_gemm)
+int dgemm_fit_split(const GemmParams& p, bool have_ws, size_t ws_bytes);
 int dgemm(const GemmDesc& d, hipStream_t st, double* ws, size_t ws_bytes);
 
 }  // namespace xt
