@@ -345,7 +345,13 @@ int xt_int3c2e_cart(int npair, const int* pair_info, const double* pair_prim, co
    diagonal (ab|ab) (diag = 1: one block per bra pair with ket = the same table
    entry, nket == npair) and the pivot columns (all pairs | chosen pairs) through it.
    q_bra / q_ket (device, per table entry; both or neither): blocks with
-   q_bra[k] q_ket[j] < q_thr are skipped (left zero). */
+   q_bra[k] q_ket[j] < q_thr are skipped (left zero).
+   lmax_orb and lket size the kernel's private arrays (the bucket 2 lmax_orb <= 4 and
+   2 lmax_orb + lket <= 8, or the full one).  The tables are device memory, so the
+   per-entry values are not checked; every entry must satisfy the declared bounds:
+   la, lb <= lmax_orb in every pair_info row and lc <= lket in every ket_info row.  An
+   entry above them overruns those arrays.  Declaring more than the tables hold is
+   allowed and gives the same bits. */
 int xt_int2e_cart(int npair, const int* pair_info, const double* pair_prim, const double* eab,
                   int nket, const int* ket_info, const double* ket_prim, const double* ek,
                   int lmax_orb, int lket, double omega, const double* q_bra, const double* q_ket,

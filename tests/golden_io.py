@@ -37,4 +37,6 @@ def load(name):
 
 
 def list_cases():
-    return sorted(f[:-4] for f in os.listdir(GOLDEN) if f.endswith(".npz"))
+    """The mean-field fixtures (int_ref*.npz holds the integral kernel's reference, read by
+    tests/int_cases.py)."""
+    return sorted(f[:-4] for f in os.listdir(GOLDEN) if f.endswith(".npz") and not f.startswith("int_ref"))
