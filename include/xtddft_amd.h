@@ -117,6 +117,18 @@ int xt_naux(const xt_ctx* ctx, int* naux_local, int* chol_rank);
    nr_uks_fxc_sf_tda / nr_uks_fxc_sf_tda_mc (XTDA.py:514, SF_TDA.py:90-160, 976-1047). */
 int xt_set_grid(xt_ctx* ctx, const double* ao, const double* weights,
                 const double* kernel, int ptr_kind);
+/* XTDA / UTDA only: the VV10 non-local correlation (NLC) term of the response, the
+   v1 += get_vnlc_resp(mf, mol, mo_coeff, mo_occ, dm1[0] + dm1[1]) of XTDA.py:515-517.
+   ao (4 x ngrid_nlc x nao: value, d/dx, d/dy, d/dz) on the NLC grid, its coordinates
+   (ngrid_nlc x 3, Bohr) and weights, the VV10 parameters (b, C) and the density threshold
+   rho_min (points with rho <= rho_min take no part).  Transforms the AOs to MO values,
+   forms rho0 and grad rho0 from the occupied orbitals of both spins (xt_set_orbitals must
+   have been called) and runs xt_vv10_ground once.  Afterwards xt_apply adds, per spin channel,
+   C_occ^T V1 C_vir with V1 the second derivative of the VV10 energy (see xt_vv10_response)
+   applied to the total first-order density; its time counts in the xc slot of
+   xt_last_timings.  The NLC grid is independent of xt_set_grid's. */
+int xt_set_nlc(xt_ctx* ctx, int ngrid_nlc, const double* ao, const double* coords,
+               const double* weights, double b, double C, double rho_min, int ptr_kind);
 /* XSF only: OO compression basis vects (no^2 x (no^2-1)) (XSF_TDA.py:397-414). */
 int xt_set_oo_basis(xt_ctx* ctx, const double* vects, int ptr_kind);
 
@@ -315,6 +327,39 @@ typedef struct xt_tdm_sc_desc {
 int xt_tdm_sc(const xt_tdm_sc_desc* desc, const double* op_ao, const double* c_occ_a, const double* c_vir_a,
               const double* c_occ_b, const double* c_vir_b, const double* vecs, double* out, int ptr_kind,
               void* hip_stream);
+
+/* VV10 non-local correlation on a quadrature grid: the pair sums behind the response term
+   the reference takes from pyscf.hessian.rks.get_vnlc_resp (XTDA.py:515-517).  The energy is
+     E = sum_i a_i [beta + 1/2 sum_j a_j Phi_ij],  a_i = w_i rho_i,  j = i included,
+     Phi_ij = -3/2 / (g_ij g_ji (g_ij + g_ji)),  g_ij = omega0_i R_ij^2 + kappa_i,
+     omega0 = sqrt(C gamma^2 / rho^4 + (4 pi / 3) rho),  gamma = |grad rho|^2,
+     kappa = b (3/2) pi (9 pi)^(-1/6) rho^(1/6),  beta = (3 / b^2)^(3/4) / 32,
+   over the points with rho > rho_min (a masked point is no source and receives zero).
+   What is pinned is that the device term is the exact second derivative of this energy
+   (tests/vv10_ref.py); parity with PySCF's get_vnlc_resp is not pinned.
+   Device pointers; coords (ngrid x 3), weights, rho, gamma (ngrid); targets are the window
+   [i0, i1), sources always all points.  Arguments are validated before any HIP call
+   (negative sizes, i0 <= i1 <= ngrid, b > 0, C >= 0, rho_min >= 0, null pointers where there
+   is work); an empty window (or nz = 0) returns 0 and touches nothing.  Reductions are
+   fixed-order: two calls on the same input return the same bits.
+   xt_vv10_ground: sums (6 x ngrid; the window's columns are written), with
+   T_ij = a_j / (g_ij g_ji (g_ij + g_ji)), u_ij = 1/g_ij + 1/(g_ij + g_ji):
+     F = -3/2 sum_j T_ij,  U = sum_j T_ij u_ij,  W = sum_j R_ij^2 T_ij u_ij,
+     S0, S1, S2 = sum_j a_j Phi_xx {1, R_ij^2, R_ij^4}   (Phi_xx: second derivative in g_ij);
+   dE/drho_i = w_i [beta + F + 3/2 rho_i (U dkappa/drho + W domega0/drho)],
+   dE/dgamma_i = w_i 3/2 rho_i W domega0/dgamma. */
+int xt_vv10_ground(int ngrid, const double* coords, const double* weights, const double* rho,
+                   const double* gamma, double b, double C, double rho_min, int i0, int i1,
+                   double* sums, void* hip_stream);
+/* xt_vv10_response: (vrho1, vgamma1)[v, i] = sum_j d2E/d(rho, gamma)_i d(rho, gamma)_j applied
+   to (rho1, gamma1)[v, j] for nz vectors, all four arrays (nz x ngrid) row-major; the window's
+   columns of the outputs are written.  sums is xt_vv10_ground's output for the same data (at
+   least over the window).  One kernel for every nz >= 1 and ngrid >= 1; a pair's kernel values
+   are generated once per tile of up to 24 vectors. */
+int xt_vv10_response(int ngrid, const double* coords, const double* weights, const double* rho,
+                     const double* gamma, double b, double C, double rho_min, const double* sums,
+                     int nz, const double* rho1, const double* gamma1, int i0, int i1,
+                     double* vrho1, double* vgamma1, void* hip_stream);
 
 /* mean-field front end ------------------------------ */
 /* 3-index Coulomb integrals (ab|c) over contracted Cartesian Gaussians by

@@ -31,6 +31,7 @@ EXPORTS = [
     "xt_xsf_j_diagonals", "xt_set_exchange_mode", "xt_prepare", "xt_exchange_plan", "xt_set_partition", "xt_set_profile",
     "xt_profile_stats", "xt_profile_bytes", "xt_dgemm", "xt_dgemm_strided", "xt_precond", "xt_row_norms2", "xt_row_scale", "xt_build_id",
     "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao", "xt_tdm", "xt_tdm_sc", "xt_gemm_plan", "xt_gemm_run",
+    "xt_set_nlc", "xt_vv10_ground", "xt_vv10_response",
 ]
 
 
@@ -145,6 +146,10 @@ def lib():
     pi = POINTER(c_int)
     L.xt_gemm_plan.argtypes = [POINTER(XtGemmDesc), pi, pi, pi, pi, pi, pi]
     L.xt_gemm_run.argtypes = [POINTER(XtGemmDesc), dp, dp, dp, vp]
+    L.xt_set_nlc.argtypes = [vp, c_int, dp, dp, dp, c_double, c_double, c_double, c_int]
+    L.xt_vv10_ground.argtypes = [c_int, dp, dp, dp, dp, c_double, c_double, c_double, c_int, c_int, dp, vp]
+    L.xt_vv10_response.argtypes = [c_int, dp, dp, dp, dp, c_double, c_double, c_double, dp, c_int, dp, dp,
+                                   c_int, c_int, dp, dp, vp]
     for name in EXPORTS:
         if not hasattr(L, name):
             raise LibraryMissing(f"{LIB_PATH} lacks symbol {name}")

@@ -102,6 +102,13 @@ struct xt_ctx {
   bool trimmed = false;          // the MO factor holds only this rank's aux window (xt_prepare)
   int naux_full = 0;             // desc naux before the trim
   size_t chunk_bytes = 0;        // XT_CHUNK_BYTES: cap on every chunk-loop byte budget (0: not set)
+  // VV10 non-local correlation (xt_set_nlc): its own grid, MO values on it and the ground-state data
+  bool has_nlc = false;
+  int nlc_ng = 0;
+  double nlc_b = 0.0, nlc_C = 0.0, nlc_rho_min = 0.0;
+  DevBuf nlcPhi;                 // (nbasis, 4, nlc_ng, nmo)
+  DevBuf nlcG;                   // per point: xyz (3) | w | rho0 | gamma0 | grad rho0 (3 planes) | sums (6 planes) | dE/dgamma
+  DevBuf nlcU, nlcR;             // per apply: the 4 U / L planes of a chunk; rho1, gamma1, grad rho1 (3), vrho1, vgamma1
 };
 
 // byte budget of a chunked loop: its default, capped by XT_CHUNK_BYTES when that is set
@@ -286,7 +293,7 @@ int xt_destroy(xt_ctx* c) {
   DevBuf* bufs[] = {&c->C, &c->Bmo, &c->Bmo_lr, &c->Phi, &c->kern, &c->F, &c->eps, &c->vects,
                     &c->ze, &c->acc, &c->kx, &c->zr, &c->tbuf, &c->ubuf, &c->gam, &c->gam2, &c->ws,
                     &c->stage, &c->stage2, &c->zin, &c->sout, &c->trace, &c->zp, &c->accT, &c->wbuf, &c->taubuf,
-                    &c->Kx};
+                    &c->Kx, &c->nlcPhi, &c->nlcG, &c->nlcU, &c->nlcR};
   for (DevBuf* b : bufs) b->release();
   for (int i = 0; i < 5; ++i) (void)hipEventDestroy(c->ev[i]);
   for (hipEvent_t e : c->pev) (void)hipEventDestroy(e);
@@ -321,6 +328,7 @@ int xt_set_orbitals(xt_ctx* c, const double* ca, const double* cb, int ptr_kind)
   }
   c->has_orb = true;
   c->kx_valid = false;
+  c->has_nlc = false;   // its MO values belong to the previous orbitals
   return 0;
 }
 
@@ -565,6 +573,67 @@ int xt_set_grid(xt_ctx* c, const double* ao, const double* w, const double* kern
   HIPCHK(hipStreamSynchronize(c->st));
   c->stage.release(); c->stage2.release();
   c->has_grid = true;
+  return 0;
+}
+
+// nlcG planes (each nlc_ng doubles; xyz is one block of 3 nlc_ng)
+static inline double* nlc_xyz(const xt_ctx* c) { return c->nlcG.p; }
+static inline double* nlc_plane(const xt_ctx* c, int k) { return c->nlcG.p + (size_t)(3 + k) * c->nlc_ng; }
+enum { NLC_W = 0, NLC_RHO = 1, NLC_GAM = 2, NLC_GRAD = 3, NLC_SUMS = 6, NLC_VG = 12, NLC_PLANES = 13 };
+
+int xt_set_nlc(xt_ctx* c, int ng, const double* ao, const double* coords, const double* w, double b, double C,
+               double rho_min, int ptr_kind) {
+  if (!c || !ao || !coords || !w) return fail(XT_ERR_ARG, "null argument");
+  if (c->d.kind != XT_KIND_XTDA && c->d.kind != XT_KIND_UTDA)
+    return fail(XT_ERR_ARG, "the VV10 response exists for XTDA / UTDA only (XTDA.py:515-517)");
+  if (ng <= 0 || !(b > 0.0) || !(C >= 0.0) || !(rho_min >= 0.0))
+    return fail(XT_ERR_ARG, "xt_set_nlc: need ngrid_nlc > 0, b > 0, C >= 0, rho_min >= 0");
+  if (!c->has_orb) return fail(XT_ERR_STATE, "xt_set_orbitals must precede xt_set_nlc");
+  (void)hipSetDevice(c->d.device);
+  c->has_nlc = false;
+  const int nao = c->d.nao, nmo = c->d.nmo;
+  c->nlc_ng = ng; c->nlc_b = b; c->nlc_C = C; c->nlc_rho_min = rho_min;
+  RET(c->nlcPhi.ensure((size_t)c->nbasis * 4 * ng * nmo));
+  RET(c->nlcG.ensure((size_t)(3 + NLC_PLANES) * ng));
+  const hipMemcpyKind k = ptr_kind == XT_PTR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+  HIPCHK(hipMemcpyAsync(nlc_xyz(c), coords, (size_t)3 * ng * 8, k, c->st));
+  HIPCHK(hipMemcpyAsync(nlc_plane(c, NLC_W), w, (size_t)ng * 8, k, c->st));
+  const size_t gchunk_max = chunk_budget(c, (size_t)1 << 30) / (8 * (size_t)nao);
+  int gc = (int)(gchunk_max < (size_t)ng ? gchunk_max : ng);
+  if (gc < 1) gc = 1;
+  if (ptr_kind == XT_PTR_HOST) RET(c->stage.ensure((size_t)gc * nao));
+  for (int comp = 0; comp < 4; ++comp) {
+    for (int g0 = 0; g0 < ng; g0 += gc) {
+      const int n = (g0 + gc <= ng) ? gc : ng - g0;
+      const double* src = ao + ((size_t)comp * ng + g0) * nao;
+      if (ptr_kind == XT_PTR_HOST) {
+        HIPCHK(hipMemcpyAsync(c->stage.p, src, (size_t)n * nao * 8, hipMemcpyHostToDevice, c->st));
+        src = c->stage.p;
+      }
+      for (int bs = 0; bs < c->nbasis; ++bs) {
+        GemmDesc g;
+        g.M = n; g.N = nmo; g.K = nao;
+        g.A = src; g.sAm = nao; g.sAk = 1;
+        g.B = c->C.p + (size_t)bs * nao * nmo; g.sBk = nmo; g.sBn = 1;
+        g.C = c->nlcPhi.p + (((size_t)bs * 4 + comp) * ng + g0) * nmo; g.ldc = nmo;
+        RET(gemm(c, g));
+      }
+    }
+  }
+  const long compP = (long)ng * nmo;
+  const double* PA = c->nlcPhi.p;
+  const double* PB = c->nlcPhi.p + (size_t)c->occ_basis[1] * 4 * compP;
+  vv10_rho0(c->st, ng, nmo, compP, PA, c->d.nc + c->d.no, PB, c->d.nc, nlc_plane(c, NLC_RHO),
+            nlc_plane(c, NLC_GRAD), nlc_plane(c, NLC_GAM));
+  RET(xt_vv10_ground(ng, nlc_xyz(c), nlc_plane(c, NLC_W), nlc_plane(c, NLC_RHO), nlc_plane(c, NLC_GAM), b, C,
+                     rho_min, 0, ng, nlc_plane(c, NLC_SUMS), c->st));
+  vv10_vgamma0(c->st, ng, nlc_plane(c, NLC_W), nlc_plane(c, NLC_RHO), nlc_plane(c, NLC_GAM),
+               nlc_plane(c, NLC_SUMS), b, C, rho_min, nlc_plane(c, NLC_VG));
+  HIPCHK(hipStreamSynchronize(c->st));
+  c->stage.release();
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(XT_ERR_HIP, std::string("xt_set_nlc kernel error: ") + hipGetErrorString(e));
+  c->has_nlc = true;
   return 0;
 }
 
@@ -1227,6 +1296,85 @@ static int xc_response(xt_ctx* c, int nz) {
 }
 
 // ---------------------------------------------------------------------------
+// VV10 (NLC) response over the NLC grid (XTDA.py:515-517), in chunks of G points:
+//   forward  Uc = {PhiV0, dPhiV_x, dPhiV_y, dPhiV_z} Ze^T            (4 GEMMs per group, tag 2)
+//            rho1, grad rho1 summed over both spin channels, gamma1 = 2 grad rho0 . grad rho1
+//   xt_vv10_response over the whole grid: (vrho1, vgamma1)
+//   back     L0 = wv0 PhiO + wv . dPhiO, Lc = wv_c PhiO;  acc += L0^T PhiV0 + sum_c Lc^T dPhiV_c
+//                                                                     (4 GEMMs per group, tag 3)
+// The potential is the same for both spins; each channel projects it onto its own block.
+// ---------------------------------------------------------------------------
+static int nlc_response(xt_ctx* c, int nz) {
+  const int O = c->O, V = c->V, nmo = c->d.nmo, ng = c->nlc_ng, nch = c->nchan;
+  const long chs = (long)nz * O * V;
+  Group gr[2];
+  const int ngr = channel_groups(c, gr);
+  const size_t per_g = (size_t)4 * nch * nz * O;
+  size_t G = chunk_budget(c, (size_t)4 << 30) / (8 * per_g);
+  if (G > (size_t)ng) G = ng;
+  if (G < 64) G = 64 < (size_t)ng ? 64 : ng;
+  RET(c->nlcU.ensure(per_g * G));
+  RET(c->nlcR.ensure((size_t)7 * nz * ng));
+  double* rho1 = c->nlcR.p;
+  double* gam1 = rho1 + (size_t)nz * ng;
+  double* grad1 = gam1 + (size_t)nz * ng;
+  double* vr1 = grad1 + (size_t)3 * nz * ng;
+  double* vg1 = vr1 + (size_t)nz * ng;
+  const long compP = (long)ng * nmo;
+  const long basP = 4 * compP;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1)
+      RET(xt_vv10_response(ng, nlc_xyz(c), nlc_plane(c, NLC_W), nlc_plane(c, NLC_RHO), nlc_plane(c, NLC_GAM),
+                           c->nlc_b, c->nlc_C, c->nlc_rho_min, nlc_plane(c, NLC_SUMS), nz, rho1, gam1, 0, ng, vr1,
+                           vg1, c->st));
+    for (int g0 = 0; g0 < ng; g0 += (int)G) {
+      const int n = (g0 + (int)G <= ng) ? (int)G : ng - g0;
+      const long tcs = (long)nch * nz * O * n;
+      double* Ug[2]; long ldU[2];
+      for (int q = 0; q < ngr; ++q) {
+        Ug[q] = c->nlcU.p + (long)gr[q].ch0 * nz * O * n;
+        ldU[q] = (long)gr[q].nch * nz * O;
+      }
+      // spin s -> (group, row offset inside the group)
+      double* Us[2]; long lus[2]; const double* Ps[2];
+      for (int s = 0; s < 2; ++s) {
+        const int q = (ngr == 1) ? 0 : s;
+        Us[s] = Ug[q] + (long)((ngr == 1) ? s : 0) * nz * O; lus[s] = ldU[q];
+        Ps[s] = c->nlcPhi.p + c->occ_basis[s] * basP + (long)g0 * nmo;
+      }
+      if (pass == 1)
+        vv10_back_l(c->st, n, g0, ng, nz, O, nmo, compP, Ps[0], Ps[1], Us[0], lus[0], Us[1], lus[1], tcs,
+                    nlc_plane(c, NLC_GRAD), nlc_plane(c, NLC_VG), vr1, vg1, grad1);
+      for (int q = 0; q < ngr; ++q) {
+        const int nzg = gr[q].nch * nz;
+        const double* PV = c->nlcPhi.p + gr[q].vb * basP + (long)g0 * nmo + c->v0;
+        for (int cc = 0; cc < 4; ++cc) {
+          GemmDesc g;
+          if (pass == 0) {   // Ucc[g][(x,i)] = sum_a PVcc[g][a] Ze[(x,i)][a]
+            g.M = n; g.N = nzg * O; g.K = V;
+            g.A = PV + cc * compP; g.sAm = nmo; g.sAk = 1;
+            g.B = c->ze.p + gr[q].ch0 * chs; g.sBn = V; g.sBk = 1;
+            g.C = Ug[q] + cc * tcs; g.ldc = ldU[q];
+            g.tag = 2;
+          } else {           // acc[(x,i)][a] += sum_g Lcc[g][(x,i)] PVcc[g][a]
+            g.M = nzg * O; g.N = V; g.K = n;
+            g.A = Ug[q] + cc * tcs; g.sAm = 1; g.sAk = ldU[q];
+            g.B = PV + cc * compP; g.sBk = nmo; g.sBn = 1;
+            g.C = c->acc.p + gr[q].ch0 * chs; g.ldc = V; g.beta = 1.0;
+            g.tag = 3;
+          }
+          RET(gemm(c, g));
+        }
+      }
+      if (pass == 0)
+        vv10_forward(c->st, n, g0, ng, nz, O, nmo, compP, Ps[0], Ps[1], Us[0], lus[0], Us[1], lus[1], tcs,
+                     nlc_plane(c, NLC_GRAD), rho1, gam1, grad1);
+    }
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // XSF spin-adaptation Delta-A (XSF_TDA.py:1175-1274), ROKS only
 // full-space blocks: rows [0,nc) core / [nc,O) open ; cols [0,no) open / [no,V) virtual
 // ---------------------------------------------------------------------------
@@ -1445,6 +1593,7 @@ extern "C" int xt_apply(xt_ctx* c, int nz, const double* z, double* sigma, int p
 
   // ---- XC ----------------------------------------------------------------------
   if (d.xctype != XT_XC_NONE && d.ngrid > 0) RET(xc_response(c, nz));
+  if (c->has_nlc) RET(nlc_response(c, nz));
   for (int q = 0; q < ngrp; ++q)   // acc_g += accT_g (left-contraction results)
     permute_add(c->st, grp[q].nch * nz, O, V, 1.0, c->accT.p + grp[q].ch0 * chs, c->acc.p + grp[q].ch0 * chs);
   HIPCHK(hipEventRecord(c->ev[3], c->st));

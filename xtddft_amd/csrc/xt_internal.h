@@ -172,6 +172,19 @@ int eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info, 
             hipStream_t st);
 int xc_rho_w(int O, int nx, int V, int n, const double* PO, long ldp, const double* Z, long zi, long zx,
              const double* W, long wc, long wg, double* R, long rg, hipStream_t st);
+// point kernels of the context's VV10 (NLC) path (xt_vv10.hip): MO values on the NLC grid at
+// P[c compP + g nmo + p]; the U / L planes (value, x, y, z) of a chunk lie tcs doubles apart;
+// grad rho0 (3, Gn), rho1 / gamma1 / vrho1 / vgamma1 (nz, Gn), grad rho1 (3, nz, Gn)
+void vv10_rho0(hipStream_t st, int n, int nmo, long compP, const double* PA, int nocc_a, const double* PB,
+               int nocc_b, double* rho, double* grad, double* gam);
+void vv10_vgamma0(hipStream_t st, int n, const double* w, const double* rho, const double* gam, const double* sums,
+                  double b, double C, double rho_min, double* vg);
+void vv10_forward(hipStream_t st, int n, int g0, int Gn, int nz, int O, int nmo, long compP, const double* P0,
+                  const double* P1, double* U0, long ld0, double* U1, long ld1, long tcs, const double* grad0,
+                  double* rho1, double* gam1, double* grad1);
+void vv10_back_l(hipStream_t st, int n, int g0, int Gn, int nz, int O, int nmo, long compP, const double* P0,
+                 const double* P1, double* L0, long ld0, double* L1, long ld1, long tcs, const double* grad0,
+                 const double* vg0, const double* vr1, const double* vg1, const double* grad1);
 size_t dgemm_workspace_bytes(const GemmDesc& d);
 // host only: dgemm()'s layout / addressing checks (0 or XT_ERR_ARG), and the split count it
 // launches for a planned one when handed ws_bytes of workspace (fewer splits when the slabs

@@ -44,9 +44,12 @@ class Grid:
 
     ao      : (ncomp, ngrid, nao)  ncomp = 1 (LDA) or 4 (GGA: value, d/dx, d/dy, d/dz)
     weights : (ngrid,)
+    coords  : optional (ngrid, 3) point coordinates in Bohr (the VV10 grid needs them:
+              its kernel depends on the distance between points)
     """
     ao: np.ndarray
     weights: np.ndarray
+    coords: Optional[np.ndarray] = None
 
     @property
     def ngrid(self) -> int:
@@ -96,6 +99,10 @@ class MeanField:
                ``cache_xc_kernel_sf_mc``, SF_TDA.py:942-974), un-weighted, over the spin
                variables (s, grad s[, tau_s]); None: computed on demand from the SCF
                density (``xtddft_amd.mcol.sf_mc_kernel``).
+    nlc      : the SCF functional carries a VV10 non-local term.  With ``nlc_pars`` (b, C) and
+               ``nlc_grids`` (a ``Grid`` with 4 AO components and coordinates; its own, coarser
+               grid) the X-TDA / U-TDA Davidson response adds the term on the device
+               (XTDA.py:515-517); ``nlc_rho_min`` is the density below which a point takes no part.
     xctype   : 'HF' | 'LDA' | 'GGA' | 'MGGA'
     omega, alpha, hyb : ``ni.rsh_and_hybrid_coeff`` (XTDA.py:501).
     """
@@ -112,6 +119,9 @@ class MeanField:
     fxc_sf: Optional[np.ndarray] = None
     fxc_sf_mc: Optional[np.ndarray] = None
     nlc: bool = False          # the SCF functional carries a VV10 non-local term (mf.do_nlc())
+    nlc_pars: Optional[tuple] = None
+    nlc_grids: Optional[Grid] = None
+    nlc_rho_min: float = 1e-8
     cderi_lr: Optional[np.ndarray] = None
     xc: str = "synthetic"
     xctype: str = "GGA"

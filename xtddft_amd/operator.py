@@ -258,7 +258,25 @@ class DeviceOperator:
             if not (kao == kw == kk):
                 raise TypeError("grid arrays must all be host or all device")
             _capi.check(L.xt_set_grid(h, pao, pw, pk, kao), "xt_set_grid")
-        self._lap("grid", t)
+        t = self._lap("grid", t)
+        # VV10 response (XTDA.py:515-517).  Of a sharded operator only the rank that adds the
+        # local terms carries it, whole: sigma is all-reduced afterwards (the pair sum is not sharded)
+        if (self.kind in ("XTDA", "UTDA") and mf.nlc and mf.nlc_pars is not None and mf.nlc_grids is not None
+                and self.desc.add_local):
+            ng = mf.nlc_grids
+            if ng.coords is None or ng.ncomp != 4:
+                raise ValueError("nlc_grids needs 4 AO components (value and gradient) and coordinates")
+            arrs = [ng.ao, ng.coords, ng.weights]
+            if _is_device(ng.ao):
+                torch = _torch()
+                arrs = [x if _is_device(x) else torch.as_tensor(np.ascontiguousarray(x), device=ng.ao.device)
+                        for x in arrs]
+            (pao, kao, rao), (pc, kc, rc), (pw, kw, rw) = (_ptr(x) for x in arrs)
+            if not (kao == kc == kw):
+                raise TypeError("NLC grid arrays must all be host or all device")
+            b, c_ = (float(x) for x in mf.nlc_pars)
+            _capi.check(L.xt_set_nlc(h, ng.ngrid, pao, pc, pw, b, c_, float(mf.nlc_rho_min), kao), "xt_set_nlc")
+            self._lap("nlc", t)
 
     def naux(self):
         """(DF / Cholesky functions on this rank, full Cholesky rank of an ERI8 factorisation)."""

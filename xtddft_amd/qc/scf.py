@@ -28,20 +28,30 @@ import dataclasses
 import numpy as np
 import scipy.linalg
 
+from . import nlc as _nlc
 from . import xc as _xc
 from .grid import gen_grids
 from .gto import C2V_IRREPS
 
 XC_BLOCK = 16384
+# Default VV10 grid per atom: (radial points, Lebedev size) for atomic_grid.  A choice of this
+# front end (coarser than the XC grid, as VV10 grids usually are); NOT PySCF's nlcgrids level.
+NLC_GRID = (35, 110)
 INCORE_MAX_NAO = 200      # eri_mode 'auto' on a GPU: stored ERIs up to this size, Cholesky above
 
 
 class _SCFBase:
     restricted_open = True
 
-    def __init__(self, mol, xc: str = "HF"):
+    def __init__(self, mol, xc: str = "HF", nlc=None):
         self.mol = mol
         self.xc = xc
+        # VV10 non-local correlation on top of xc: the caller's (b, C), as PySCF's mf.nlc = 'vv10'
+        # attaches it to any functional; None: no such term.  nlc_grid: (n_rad, n_ang) per atom
+        self.nlc = None if nlc is None else (float(nlc[0]), float(nlc[1]))
+        self.nlc_grid = NLC_GRID
+        self.nlc_rho_min = _nlc.RHO_MIN
+        self.nlc_grids = None
         self.irrep_nelec = None
         self.conv_tol = 1e-10
         self.conv_tol_grad = None
@@ -150,6 +160,10 @@ class _SCFBase:
                 import torch
                 torch.cuda.synchronize(dev)
             self.timings["eval_ao_s"] = time.perf_counter() - t0
+        if self.nlc is not None:
+            if self.nlc_grids is None:
+                self.nlc_grids = _nlc.gen_nlc_grids(mol, *self.nlc_grid)
+            self.ao_nlc = np.ascontiguousarray(mol.eval_ao(self.nlc_grids.coords, deriv=1))
         if self._device is not None:
             from .device import DeviceEngine
             self.device_engine = DeviceEngine(self, self._device)
@@ -280,7 +294,18 @@ class _SCFBase:
                 veff = veff - self.hyb * vk
                 exc -= 0.5 * self.hyb * (np.sum(dms[0] * vk[0]) + np.sum(dms[1] * vk[1]))
         ecoul = 0.5 * np.sum((dms[0] + dms[1]) * vj)
+        if self.nlc is not None:    # the same potential for both spins; E_nlc counts as XC energy
+            e_nlc, v_nlc = self._vnlc(dms[0] + dms[1])
+            veff = veff + v_nlc[None]
+            exc += e_nlc
         return veff, float(ecoul), float(exc)
+
+    def _vnlc(self, dm):
+        """(E_nlc, V_nlc) of the total density matrix; after to_device() the pair sums come
+        from the library (xt_vv10_ground), otherwise from NumPy."""
+        g = self.nlc_grids
+        return _nlc.nlc_vmat(self.ao_nlc, g.coords, g.weights, dm, *self.nlc, rho_min=self.nlc_rho_min,
+                             device=self._device)
 
     def get_veff_hf(self, dm):
         """Pure-HF potential J - K at dm (``scf.ROHF(mol).get_veff``, XTDA.py:608-612)."""
@@ -334,8 +359,8 @@ class _SCFBase:
 class ROHF(_SCFBase):
     """Restricted open-shell HF; ``ROKS`` sets a functional."""
 
-    def __init__(self, mol, xc: str = "HF"):
-        super().__init__(mol, xc)
+    def __init__(self, mol, xc: str = "HF", nlc=None):
+        super().__init__(mol, xc, nlc)
 
     @staticmethod
     def get_roothaan_fock(fa, fb, dma, dmb, s):
@@ -446,8 +471,8 @@ class UHF(_SCFBase):
     """Unrestricted HF; ``UKS`` sets a functional."""
     restricted_open = False
 
-    def __init__(self, mol, xc: str = "HF"):
-        super().__init__(mol, xc)
+    def __init__(self, mol, xc: str = "HF", nlc=None):
+        super().__init__(mol, xc, nlc)
 
     def _occ(self, es, labs):
         counts = self._irrep_counts()
@@ -554,14 +579,15 @@ class UHF(_SCFBase):
         return _meanfield(self, chol_tol)
 
 
-def ROKS(mol, xc: str = "LDA"):
+def ROKS(mol, xc: str = "LDA", nlc=None):
     """``dft.ROKS(mol)``; set ``.xc`` before ``kernel()`` (default kept as PySCF's 'LDA,VWN'
-    is not implemented: pass the functional explicitly)."""
-    return ROHF(mol, xc)
+    is not implemented: pass the functional explicitly).  ``nlc=(b, C)`` adds the VV10
+    non-local correlation with those parameters (``qc.nlc``)."""
+    return ROHF(mol, xc, nlc)
 
 
-def UKS(mol, xc: str = "LDA"):
-    return UHF(mol, xc)
+def UKS(mol, xc: str = "LDA", nlc=None):
+    return UHF(mol, xc, nlc)
 
 
 def _diis(fs, errs):
@@ -657,6 +683,11 @@ def _meanfield(mf, chol_tol):
                     cderi=cderi, grids=grids, fxc=fxc, fxc_sf=fxc_sf, xc=mf.xc,
                     xctype=mf.xctype, omega=omega, alpha=alpha, hyb=hyb, eri=eri8,
                     cderi_lr=cderi_lr, eri_lr=eri8_lr, e_tot=mf.e_tot)
+    if mf.nlc is not None:
+        g = mf.nlc_grids
+        out.nlc, out.nlc_pars, out.nlc_rho_min = True, mf.nlc, mf.nlc_rho_min
+        out.nlc_grids = Grid(ao=mf.ao_nlc, weights=np.ascontiguousarray(g.weights),
+                             coords=np.ascontiguousarray(g.coords))
     out.extra.update(dict(s1e=mf.s1e, orbsym=getattr(mf, "orbsym", None), qc_mol=mol))
     if not mf.restricted_open:
         out.extra["spin_square"] = mf.spin_square()

@@ -67,14 +67,18 @@ NLC_SF_WARNING = ('NLC functional found in DFT object.  Its second derivative is
 
 def nlc_check(mf, davidson_xtda=False):
     """The reference's treatment of a VV10 (NLC) functional: the X-TDA / U-TDA Davidson
-    response adds ``get_vnlc_resp`` (XTDA.py:515-517), which is not built here, so that path
-    refuses; every other path (explicit X-TDA A, XTDA.py:166-169; SF-TDA, SF_TDA.py:490-493,
+    response adds ``get_vnlc_resp`` (XTDA.py:515-517).  The device operator adds the term when
+    the mean field carries its data (``nlc_pars`` and ``nlc_grids``); without them that path
+    refuses.  Every other path (explicit X-TDA A, XTDA.py:166-169; SF-TDA, SF_TDA.py:490-493,
     669-672, 869-872; XSF-TDA through the same kernels) leaves it out with this warning."""
     if not getattr(mf, "nlc", False):
         return
     if davidson_xtda:
+        if getattr(mf, "nlc_pars", None) is not None and getattr(mf, "nlc_grids", None) is not None:
+            return
         raise NotImplementedError("the VV10 (NLC) response term of the X-TDA Davidson path "
-                                  "(XTDA.py:515-517, pyscf.hessian.rks.get_vnlc_resp) is not built; "
+                                  "(XTDA.py:515-517, pyscf.hessian.rks.get_vnlc_resp) needs the mean field's "
+                                  "nlc_pars and nlc_grids; "
                                   "use_Davidson=False runs the explicit A, which leaves it out as the "
                                   "reference does")
     import warnings
