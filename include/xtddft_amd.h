@@ -361,6 +361,79 @@ int xt_vv10_response(int ngrid, const double* coords, const double* weights, con
                      int nz, const double* rho1, const double* gamma1, int i0, int i1,
                      double* vrho1, double* vgamma1, void* hip_stream);
 
+/* Simplified open-shell TDA (sX-TDA / sU-TDA, xtddft/sTDA/os_sTDA.py) ------------------------
+   Everything is in the active space: spin alpha has nocc_a = nc + no occupied and nvir_a = nv
+   virtual orbitals, spin beta nocc_b = nc and nvir_b = no + nv.  A CSF is a triple (s, i, a):
+   spin (0 alpha, 1 beta), occupied and virtual index in that spin's numbering; the classes are
+   CV(aa) s = 0, i < nc; OV(aa) s = 0, i >= nc; CO(bb) s = 1, a < no; CV(bb) s = 1, a >= no.
+   With the Loewdin charges q^A_pq = sum_{mu in A} C'_mu,p C'_mu,q (C' = S^1/2 C) and the
+   Mataga-Nishimoto-Ohno-Klopman matrices gammaK, gammaJ (OSsTDA.gamma, os_sTDA.py:408-433)
+     A[p,q] =  sum_AB q_ov[s_p][A,i_p,a_p] gammaK[A,B] q_ov[s_q][B,i_q,a_q]
+             - d(s_p,s_q) sum_AB q_oo[s][A,i_p,i_q] gammaJ[A,B] q_vv[s][B,a_p,a_q]
+             + d(s_p,s_q) (d(i_p,i_q) F_vv[s][a_p,a_q] - d(a_p,a_q) F_oo[s][i_p,i_q])
+             + X(p,q)                                   (spin_adapted, no > 0, both CSFs of class CV)
+             + d(p,q) delta_max / (1 + (K_pp / sigma_k)^4)                         (correct = 1)
+   K_pp the first line at p = q.  X, with c1 = (1 - sqrt((S+1)/S) + 1/(2S))/2,
+   c2 = (-1 + sqrt((S+1)/S) + 1/(2S))/2, c3 = 1/(4S), S = si, the ROHF-type Fock blocks H and the
+   alpha virtual index a (beta: no + a): D_ab = H_b,vv[no+a,no+b] - H_a,vv[a,b],
+   D_ij = H_b,oo[i,j] - H_a,oo[i,j];  CV(aa)-CV(aa): c1 d_ij D_ab + c2 d_ab D_ij;
+   CV(bb)-CV(bb): c2 d_ij D_ab + c1 d_ab D_ij;  CV(aa)-CV(bb): c3 (d_ij D_ab + d_ab D_ij)
+   (os_sTDA.py:263-325, 703-723).
+   Numeric operands and outputs are device pointers in a pair-major layout (the natm charges of an
+   orbital pair are contiguous); CSF lists and the atom AO offsets are HOST int arrays, so that
+   every index is checked before the first HIP call (XT_ERR_ARG: negative sizes, an index outside
+   its block, a null pointer where there is work, si <= 0 with spin_adapted and no > 0).  Empty
+   work returns 0 and touches nothing.  Reductions are fixed-order: two calls on the same input
+   return the same bits.
+   Device and stream: the entries allocate on the CURRENT HIP device (the uploaded CSF lists and
+   AO offsets; xt_stda_half's GEMM workspace), so the caller makes the device that owns the
+   operands and hip_stream current before the call (hipSetDevice; torch.cuda.device).  Every
+   call with work BLOCKS: it allocates, copies its host lists, launches on hip_stream,
+   synchronises that stream and frees before it returns (xt_stda_half has no list: it queues
+   engine GEMMs like xt_dgemm and may return before they finish).  The stream argument only orders the
+   call against earlier work on that stream; a stream under graph capture cannot be used. */
+typedef struct xt_stda_desc {
+  int natm;
+  int nocc_a, nvir_a, nocc_b, nvir_b;
+  int nc, no, nv;       /* spin_adapted: nocc_a = nc + no, nvir_a = nv, nocc_b = nc, nvir_b = no + nv */
+  int spin_adapted;     /* 1: the X term (ROKS) */
+  double si;            /* S of the reference (mol.spin / 2) */
+  int correct;          /* 1: the diagonal correction */
+  double delta_max, sigma_k;
+} xt_stda_desc;
+/* device operands of the element generator, per spin (a spin no CSF uses may be null):
+   q_ov, k_ov = gammaK q_ov  [(i nvir + a) natm + A];  q_oo [(i nocc + j) natm + A];
+   j_vv = gammaJ q_vv [(a nvir + b) natm + A];  f_oo (nocc x nocc), f_vv (nvir x nvir) the KS Fock
+   blocks;  h_oo, h_vv the ROHF-type Fock blocks (spin_adapted with no > 0 only). */
+typedef struct xt_stda_ops {
+  const double *q_ov_a, *k_ov_a, *q_oo_a, *j_vv_a, *f_oo_a, *f_vv_a, *h_oo_a, *h_vv_a;
+  const double *q_ov_b, *k_ov_b, *q_oo_b, *j_vv_b, *f_oo_b, *f_vv_b, *h_oo_b, *h_vv_b;
+} xt_stda_ops;
+/* q_oo / q_ov / q_vv of one spin from cprime (nao x (nocc + nvir), occupied columns first, device)
+   and the host offsets ao_off[natm + 1] of each atom's contiguous AOs (an atom may have one AO or
+   none).  Replaces the per-atom einsum loop of os_sTDA.py:644-670. */
+int xt_stda_charges(const xt_stda_desc* desc, int spin, int nao, const int* ao_off, const double* cprime,
+                    double* q_oo, double* q_ov, double* q_vv, void* hip_stream);
+/* k_ov = q_ov gammaK and j_vv = q_vv gammaJ of one spin (gamma symmetric natm x natm, device):
+   engine GEMMs over the pair rows.  Replaces the gamma_k / gamma_j operands of every einsum in
+   os_sTDA.py:33-44, 235-260, 263-325. */
+int xt_stda_half(const xt_stda_desc* desc, int spin, const double* gamma_k, const double* gamma_j,
+                 const double* q_ov, const double* q_vv, double* k_ov, double* j_vv, void* hip_stream);
+/* e[p] = A[p,p] and kpp[p] = K_pp (kpp may be null) for a host list csf[3 n] of (s, i, a): the
+   bits of xt_stda_matrix's diagonal on the same list.  Replaces iaia_f and the spin-adapted and
+   correction additions, os_sTDA.py:33-44, 686-731. */
+int xt_stda_diag(const xt_stda_desc* desc, const xt_stda_ops* ops, int n, const int* csf, double* e,
+                 double* kpp, void* hip_stream);
+/* w[q] = sum_{p in P} B[p,q]^2 / (e_n[q] - e_p[p] + 1e-10) for every q of the N list, B the first
+   two lines of the generator; the P x N block is never stored.  Replaces the joblib loops over
+   iajb_f, os_sTDA.py:235-260, 752-793. */
+int xt_stda_select(const xt_stda_desc* desc, const xt_stda_ops* ops, int n_p, const int* csf_p,
+                   const double* e_p, int n_n, const int* csf_n, const double* e_n, double* w, void* hip_stream);
+/* The dense A (n x n, row-major, both triangles computed) of a CSF list in any order.  Replaces
+   constractA and the block loops of os_sTDA.py:263-350, 1014-1221. */
+int xt_stda_matrix(const xt_stda_desc* desc, const xt_stda_ops* ops, int n, const int* csf, double* a,
+                   void* hip_stream);
+
 /* mean-field front end ------------------------------ */
 /* 3-index Coulomb integrals (ab|c) over contracted Cartesian Gaussians by
    McMurchie-Davidson (replaces libcint int3c2e behind PySCF df.incore.aux_e2,

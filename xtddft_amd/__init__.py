@@ -7,6 +7,7 @@ Reference-compatible entry points (PySCF-style operator API):
   ``gen_tda_operation_sf``, ``init_guess``, ``davidson_process``
 * ``XSF_TDA(mf, SA, ...)``              (xtddft/XSF_TDA.py)
 * ``davidson1``                         (xtddft/utils/Davidson.py)
+* ``OSsTDA(mol, mf, ...)``              (xtddft/sTDA/os_sTDA.py)
 
 The arithmetic runs in the HIP library ``_lib/libxtddft_amd.so`` (C ABI in
 ``include/xtddft_amd.h``); there is no CPU fallback.
@@ -15,7 +16,7 @@ from .meanfield import Grid, MeanField, Mole
 from .utils import HA2EV, HA2EV_XSF, order_pyscf2my, so2st, st2so
 
 __all__ = ["Grid", "MeanField", "Mole", "HA2EV", "HA2EV_XSF", "order_pyscf2my", "so2st", "st2so",
-           "XTDA", "SF_TDA", "SF_TDA_up", "SF_TDA_down", "XSF_TDA", "davidson1", "DeviceOperator"]
+           "XTDA", "SF_TDA", "SF_TDA_up", "SF_TDA_down", "XSF_TDA", "davidson1", "DeviceOperator", "OSsTDA"]
 
 
 def __getattr__(name):   # lazy: importing the package must not require a GPU
@@ -31,6 +32,9 @@ def __getattr__(name):   # lazy: importing the package must not require a GPU
     if name == "davidson1":
         from .davidson import davidson1
         return davidson1
+    if name == "OSsTDA":
+        from .stda import OSsTDA
+        return OSsTDA
     if name == "DeviceOperator":
         from .operator import DeviceOperator
         return DeviceOperator

@@ -32,6 +32,7 @@ EXPORTS = [
     "xt_profile_stats", "xt_profile_bytes", "xt_dgemm", "xt_dgemm_strided", "xt_precond", "xt_row_norms2", "xt_row_scale", "xt_build_id",
     "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao", "xt_tdm", "xt_tdm_sc", "xt_gemm_plan", "xt_gemm_run",
     "xt_set_nlc", "xt_vv10_ground", "xt_vv10_response",
+    "xt_stda_charges", "xt_stda_half", "xt_stda_diag", "xt_stda_select", "xt_stda_matrix",
 ]
 
 
@@ -61,6 +62,23 @@ class XtTdmScDesc(ctypes.Structure):
         ("ncomp", c_int), ("nstates", c_int), ("spin_adapted", c_int), ("no", c_int), ("si", c_double),
         ("with_ground", c_int),
     ]
+
+
+class XtStdaDesc(ctypes.Structure):
+    """xt_stda_desc: active-space counts and the switches of the sTDA element generator."""
+    _fields_ = [
+        ("natm", c_int), ("nocc_a", c_int), ("nvir_a", c_int), ("nocc_b", c_int), ("nvir_b", c_int),
+        ("nc", c_int), ("no", c_int), ("nv", c_int), ("spin_adapted", c_int), ("si", c_double),
+        ("correct", c_int), ("delta_max", c_double), ("sigma_k", c_double),
+    ]
+
+
+STDA_OPS = ("q_ov", "k_ov", "q_oo", "j_vv", "f_oo", "f_vv", "h_oo", "h_vv")
+
+
+class XtStdaOps(ctypes.Structure):
+    """xt_stda_ops: device addresses of the generator's operands, alpha then beta."""
+    _fields_ = [(f"{n}_{s}", c_void_p) for s in "ab" for n in STDA_OPS]
 
 
 class XtGemmDesc(ctypes.Structure):
@@ -150,6 +168,12 @@ def lib():
     L.xt_vv10_ground.argtypes = [c_int, dp, dp, dp, dp, c_double, c_double, c_double, c_int, c_int, dp, vp]
     L.xt_vv10_response.argtypes = [c_int, dp, dp, dp, dp, c_double, c_double, c_double, dp, c_int, dp, dp,
                                    c_int, c_int, dp, dp, vp]
+    sd, so = POINTER(XtStdaDesc), POINTER(XtStdaOps)
+    L.xt_stda_charges.argtypes = [sd, c_int, c_int, pi, dp, dp, dp, dp, vp]
+    L.xt_stda_half.argtypes = [sd, c_int, dp, dp, dp, dp, dp, dp, vp]
+    L.xt_stda_diag.argtypes = [sd, so, c_int, pi, dp, dp, vp]
+    L.xt_stda_select.argtypes = [sd, so, c_int, pi, dp, c_int, pi, dp, dp, vp]
+    L.xt_stda_matrix.argtypes = [sd, so, c_int, pi, dp, vp]
     for name in EXPORTS:
         if not hasattr(L, name):
             raise LibraryMissing(f"{LIB_PATH} lacks symbol {name}")
