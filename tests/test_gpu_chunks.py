@@ -1,4 +1,5 @@
-"""GPU: the chunked loops of xt_ctx.hip against the oracle.
+"""GPU: the chunked loops of the operator context (xt_ctx_jk.hip over the auxiliary index,
+xt_ctx_xc.hip over the grid) against the oracle.
 
 xt_apply and its setters walk the grid and the auxiliary (DF) index in chunks whose sizes
 follow from fixed byte budgets (8 GiB for the XC buffers, 1 GiB for the AO -> MO grid
@@ -13,7 +14,8 @@ these budgets.  All cases here (but test_chunk_floors) run with XT_CHUNK_BYTES =
 compare sigma with the oracle's vind on the same make_mf data at the suite's tolerance (1e-12 relative max-norm,
 RTOL of test_gpu_parity.py; ERI8_TOL for the stored-ERI case).
 
-`plan()` restates the chunk rule of xt_ctx.hip (budget = min(default, XT_CHUNK_BYTES); the
+`plan()` restates the chunk rules of xt_ctx_jk.hip and xt_ctx_xc.hip (budget = min(default,
+XT_CHUNK_BYTES), chunk_budget in xt_ctx.h; project_ao and grid_chunk for the grid; the
 floors of one aux row, one grid row and 64 XC points).  Every test asserts from it that the
 loops it means to exercise take at least 3 chunks with a ragged last one, so a change of
 the shapes or of the rule cannot turn a case into a single-chunk run unnoticed.  With five
@@ -66,7 +68,7 @@ def env():
             os.environ[k] = v
 
 
-# ---- the chunk rule of xt_ctx.hip, restated ---------------------------------------------
+# ---- the chunk rules of xt_ctx_jk.hip / xt_ctx_xc.hip, restated -------------------------
 def _split(total, size):
     """(chunk length, number of chunks, length of the last chunk)"""
     n = -(-total // size)

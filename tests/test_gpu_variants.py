@@ -2,8 +2,8 @@
 oracle, and the XSF exchange through the stored matrix at the row counts that take
 its 160-row streaming tile and its batching.
 
-Automatic selection (xt_ctx.hip): the dedicated M-backward kernel (xt_xcm.hip) for
-O <= 128 and the generic engine's fused mode 2 above; the dedicated rho-forward
+Automatic selection (xc_response, xt_ctx_xc.hip): the dedicated M-backward kernel
+(xt_xcm.hip) for O <= 128 and the generic engine's fused mode 2 above; the dedicated rho-forward
 kernel (xt_xcw.hip) for O > 64, the small-O rho-forward kernel (xt_xcws.hip) for
 O <= 48 from 8 trial pairs, and the engine's fused mode 1 in between.
 The two test hooks (environment, read once at xt_create) force either side outside

@@ -31,6 +31,18 @@ def test_library_builds_and_exports_every_header_symbol(hiplib):
     assert hiplib.xt_abi_version() == ABI_VERSION == 8
 
 
+def test_build_lists_every_source_and_header():
+    """Every *.hip under csrc/ is compiled and every *.h under csrc/ is in the source hash:
+    a file missing from build.SOURCES is never linked, one missing from build.HEADERS
+    silently drops out of the build id and the staleness check."""
+    from xtddft_amd import build
+    files = os.listdir(build.CSRC)
+    assert sorted(f for f in files if f.endswith(".hip")) == sorted(build.SOURCES)
+    assert sorted(f for f in files if f.endswith(".h")) == sorted(h for h in build.HEADERS if "/" not in h)
+    for h in build.HEADERS:
+        assert os.path.isfile(os.path.join(build.CSRC, h)), h
+
+
 def test_desc_layout_matches_c_header(tmp_path):
     """ctypes XtDesc has the same size/offsets as the C struct (gcc on the header)."""
     from xtddft_amd._capi import XtDesc

@@ -28,9 +28,7 @@
 // xt_stda_matrix's diagonal.  No atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <string>
-#include "../../include/xtddft_amd.h"
-#include "xt_internal.h"
+#include "xt_host.h"
 
 using namespace xt;
 
@@ -252,15 +250,6 @@ __global__ void k_stda_charges(int natm, const int* __restrict__ off, int nmo, c
   }
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) \
-    return set_error(XT_ERR_HIP, (std::string(what) + ": " #x ": " + hipGetErrorString(_e)).c_str()); } while (0)
-#define RET(x) do { int _r = (x); if (_r) return _r; } while (0)
-
 int bad(const char* what, const char* msg) { return set_error(XT_ERR_ARG, (std::string(what) + ": " + msg).c_str()); }
 
 // host-only descriptor checks
@@ -335,13 +324,9 @@ Gen make_gen(const xt_stda_desc& d, const xt_stda_ops& o) {
   return g;
 }
 
-int upload_ints(const char* what, DevBuf& b, const int* src, long count, hipStream_t st) {
-  if (hipMalloc(&b.p, (size_t)count * sizeof(int)) != hipSuccess) {
-    b.p = nullptr;
-    return set_error(XT_ERR_OOM, (std::string(what) + ": hipMalloc failed for " + std::to_string(count * 4) + " bytes").c_str());
-  }
-  HIPCHK(hipMemcpyAsync(b.p, src, (size_t)count * sizeof(int), hipMemcpyHostToDevice, st));
-  return 0;
+// a host list of count ints, copied into b
+int upload_ints(const char* what, TmpMem<int>& b, const int* src, long count, hipStream_t st) {
+  return upload(b, src, (size_t)count, XT_PTR_HOST, st, what);
 }
 
 }  // namespace
@@ -363,21 +348,21 @@ extern "C" int xt_stda_charges(const xt_stda_desc* desc, int spin, int nao, cons
   if ((nocc > 0 && !q_oo) || (nocc > 0 && nvir > 0 && !q_ov) || (nvir > 0 && !q_vv)) return bad(what, "null output block");
 
   hipStream_t st = (hipStream_t)stream;
-  DevBuf off;
+  TmpMem<int> off;
   RET(upload_ints(what, off, ao_off, d.natm + 1, st));
   auto launch = [&](int p0, int np, int q0, int nq, double* out) {
     const long total = (long)np * nq * d.natm;
     if (total <= 0) return;
     long nb = (total + 255) / 256;
     if (nb > 65536) nb = 65536;
-    hipLaunchKernelGGL(k_stda_charges, dim3((unsigned)nb), dim3(256), 0, st, d.natm, (const int*)off.p, nmo, cprime, p0,
+    hipLaunchKernelGGL(k_stda_charges, dim3((unsigned)nb), dim3(256), 0, st, d.natm, off.p, nmo, cprime, p0,
                        np, q0, nq, out);
   };
   launch(0, nocc, 0, nocc, q_oo);
   launch(0, nocc, nocc, nvir, q_ov);
   launch(nocc, nvir, nocc, nvir, q_vv);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));   // the offsets are released on return
+  HIPCHK(what, hipGetLastError());
+  HIPCHK(what, hipStreamSynchronize(st));   // the offsets are released on return
   return 0;
 }
 
@@ -415,13 +400,13 @@ extern "C" int xt_stda_diag(const xt_stda_desc* desc, const xt_stda_ops* ops, in
   RET(check_ops(what, d, ops, true, n, csf, 0, nullptr));
   if (!e) return bad(what, "null output");
   hipStream_t st = (hipStream_t)stream;
-  DevBuf l;
+  TmpMem<int> l;
   RET(upload_ints(what, l, csf, 3L * n, st));
   const int nt = (n + 15) / 16;
-  hipLaunchKernelGGL(k_stda_diag, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, make_gen(d, *ops), (const int*)l.p, n,
+  hipLaunchKernelGGL(k_stda_diag, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, make_gen(d, *ops), l.p, n,
                      nt, e, kpp);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));   // the list is released on return
+  HIPCHK(what, hipGetLastError());
+  HIPCHK(what, hipStreamSynchronize(st));   // the list is released on return
   return 0;
 }
 
@@ -436,14 +421,14 @@ extern "C" int xt_stda_select(const xt_stda_desc* desc, const xt_stda_ops* ops, 
   if (!w || !e_n || (n_p > 0 && !e_p)) return bad(what, "null argument");
   RET(check_ops(what, d, ops, false, n_p, csf_p, n_n, csf_n));
   hipStream_t st = (hipStream_t)stream;
-  DevBuf lp, ln;
+  TmpMem<int> lp, ln;
   if (n_p > 0) RET(upload_ints(what, lp, csf_p, 3L * n_p, st));
   RET(upload_ints(what, ln, csf_n, 3L * n_n, st));
   const int nt = (n_n + 15) / 16;
-  hipLaunchKernelGGL(k_stda_select, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, make_gen(d, *ops), (const int*)lp.p,
-                     n_p, e_p, (const int*)ln.p, n_n, e_n, nt, w);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));   // the lists are released on return
+  hipLaunchKernelGGL(k_stda_select, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, make_gen(d, *ops), lp.p,
+                     n_p, e_p, ln.p, n_n, e_n, nt, w);
+  HIPCHK(what, hipGetLastError());
+  HIPCHK(what, hipStreamSynchronize(st));   // the lists are released on return
   return 0;
 }
 
@@ -460,10 +445,10 @@ extern "C" int xt_stda_matrix(const xt_stda_desc* desc, const xt_stda_ops* ops, 
   const long nblk = ((long)nt * nt + 3) / 4;
   if (nblk > 0x7fffffffL) return bad(what, "list too long for one launch");
   hipStream_t st = (hipStream_t)stream;
-  DevBuf l;
+  TmpMem<int> l;
   RET(upload_ints(what, l, csf, 3L * n, st));
-  hipLaunchKernelGGL(k_stda_matrix, dim3((unsigned)nblk), dim3(256), 0, st, make_gen(d, *ops), (const int*)l.p, n, nt, a);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));   // the list is released on return
+  hipLaunchKernelGGL(k_stda_matrix, dim3((unsigned)nblk), dim3(256), 0, st, make_gen(d, *ops), l.p, n, nt, a);
+  HIPCHK(what, hipGetLastError());
+  HIPCHK(what, hipStreamSynchronize(st));   // the list is released on return
   return 0;
 }

@@ -17,10 +17,7 @@
 // depends only on the descriptor, so the split-K plans and with them the bits repeat.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
-#include <string>
-#include "../../include/xtddft_amd.h"
-#include "xt_internal.h"
+#include "xt_host.h"
 
 using namespace xt;
 
@@ -124,25 +121,7 @@ __global__ void __launch_bounds__(256) k_tdm_f3(int nc, int no, int nv, double f
   for (int u = tid; u < no; u += 256) ys[(long)(nc + u) * V + u] += s;
 }
 
-// call-scoped device memory: released on every return path
-struct Tmp {
-  double* p = nullptr;
-  size_t n = 0;
-  ~Tmp() { if (p) (void)hipFree(p); }
-  int alloc(size_t count) {
-    if (count == 0) return 0;
-    if (hipMalloc(&p, count * sizeof(double)) != hipSuccess) {
-      p = nullptr;
-      return set_error(XT_ERR_OOM, ("xt_tdm: hipMalloc failed for " + std::to_string(count * 8) + " bytes").c_str());
-    }
-    n = count;
-    return 0;
-  }
-};
-
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) \
-    return set_error(XT_ERR_HIP, (std::string("xt_tdm: " #x ": ") + hipGetErrorString(_e)).c_str()); } while (0)
-#define RET(x) do { int _r = (x); if (_r) return _r; } while (0)
+const char* const what = "xt_tdm";   // message prefix
 
 }  // namespace
 
@@ -181,52 +160,33 @@ extern "C" int xt_tdm(const xt_tdm_desc* desc, const double* op_ao, const double
   const bool scaled = d.sa != 0 && no > 0;   // without an open shell no block is scaled
 
   // states per chunk: c of the column chunk and of the row chunk, Y for every component and
-  // the upload stage within the budget (XT_TDM_WS_MIB, default 768: a tuning hook, and how
-  // the tests reach the chunked path at small sizes)
-  double budget = 768.0;
-  if (const char* e = getenv("XT_TDM_WS_MIB")) { const double v = atof(e); if (v > 0.0 && v < 768.0) budget = v; }
+  // the upload stage within the budget (tdm_budget_mib)
   const double per_state = 8.0 * ((double)(X + 2) * ov + (double)dim);
-  long ns = (long)(budget * 1048576.0 / per_state);
+  long ns = (long)(tdm_budget_mib() * 1048576.0 / per_state);
   if (ns > 32768 / X) ns = 32768 / X;   // (state, component) batches of one launch: grid z
   ns = ns < 1 ? 1 : (ns > N ? N : ns);
 
   // ---- inputs on the device ----
-  Tmp b_op, b_co, b_cv, b_vt, b_out;
-  auto upload = [&](Tmp& b, const double*& p, size_t count) -> int {
-    if (!host || !p || count == 0) return 0;
-    RET(b.alloc(count));
-    HIPCHK(hipMemcpyAsync(b.p, p, count * 8, hipMemcpyHostToDevice, st));
-    p = b.p;
-    return 0;
-  };
-  RET(upload(b_op, op_ao, (size_t)X * nao * nao));
-  RET(upload(b_co, c_occ, (size_t)nao * O));
-  RET(upload(b_cv, c_vir, (size_t)nao * V));
-  if (d.oo_compressed && no > 1) RET(upload(b_vt, vects, (size_t)no * no * (no * no - 1)));
+  TmpBuf b_op, b_co, b_cv, b_vt, b_out;
+  RET(upload(b_op, op_ao, (size_t)X * nao * nao, ptr_kind, st, what));
+  RET(upload(b_co, c_occ, (size_t)nao * O, ptr_kind, st, what));
+  RET(upload(b_cv, c_vir, (size_t)nao * V, ptr_kind, st, what));
+  if (d.oo_compressed && no > 1) RET(upload(b_vt, vects, (size_t)no * no * (no * no - 1), ptr_kind, st, what));
   double* outd = out;
-  if (host) { RET(b_out.alloc((size_t)X * N * N)); outd = b_out.p; }
+  if (host) { RET(b_out.ensure((size_t)X * N * N, what)); outd = b_out.p; }
 
-  // ---- engine launches (split-K workspace grown on demand) ----
-  Tmp ws;
+  // ---- engine launches (split-K workspace grown on demand, 256 MiB cap) ----
+  TmpBuf ws;
   auto run = [&](const GemmDesc& g) -> int {
     if (g.M <= 0 || g.N <= 0 || g.nb1 <= 0 || g.nb2 <= 0) return 0;   // empty block: nothing is launched
-    size_t need = dgemm_workspace_bytes(g);
-    const size_t cap = (size_t)256 << 20;
-    if (need > cap) need = cap;
-    if (need > ws.n * 8) {
-      HIPCHK(hipStreamSynchronize(st));   // an earlier product may still reduce from it
-      if (ws.p) { (void)hipFree(ws.p); ws.p = nullptr; ws.n = 0; }
-      RET(ws.alloc(need / 8 + 1));
-    }
-    const int r = dgemm(g, st, ws.p, ws.n * 8);
-    return r ? set_error(r, "xt_tdm: GEMM launch failed") : 0;
+    return run_gemm(g, st, ws, (size_t)256 << 20, 0, what, "GEMM launch failed");
   };
 
   // ---- D_occ, D_vir for every component ----
-  Tmp b_half, b_docc, b_dvir, b_img;
-  RET(b_half.alloc((size_t)X * nao * (O > V ? O : V)));
-  RET(b_docc.alloc((size_t)X * O * O));
-  RET(b_dvir.alloc((size_t)X * V * V));
+  TmpBuf b_half, b_docc, b_dvir, b_img;
+  RET(b_half.ensure((size_t)X * nao * (O > V ? O : V), what));
+  RET(b_docc.ensure((size_t)X * O * O, what));
+  RET(b_dvir.ensure((size_t)X * V * V, what));
   auto to_mo = [&](const double* cm, int n, double* dmo) -> int {
     GemmDesc g;   // half[x] = op[x] C
     g.M = nao; g.N = n; g.K = nao; g.nb1 = X;
@@ -247,7 +207,7 @@ extern "C" int xt_tdm(const xt_tdm_desc* desc, const double* op_ao, const double
   const double *do1 = b_docc.p, *do2 = b_docc.p, *dv1 = b_dvir.p, *dv2 = b_dvir.p;
   if (scaled) {
     const size_t so = (size_t)X * O * O, sv = (size_t)X * V * V;
-    RET(b_img.alloc(2 * so + 2 * sv));
+    RET(b_img.ensure(2 * so + 2 * sv, what));
     double* p = b_img.p;
     hipLaunchKernelGGL(k_tdm_images, dim3(nblocks((long)so)), dim3(256), 0, st, (long)X, O, nc, f1, f2, b_docc.p, p, p + so);
     hipLaunchKernelGGL(k_tdm_images, dim3(nblocks((long)sv)), dim3(256), 0, st, (long)X, V, no, f1, f2, b_dvir.p,
@@ -257,16 +217,16 @@ extern "C" int xt_tdm(const xt_tdm_desc* desc, const double* op_ao, const double
 
   // ---- state chunks ----
   const bool own_c = host || blocks;          // otherwise a chunk's c is the caller's rows
-  Tmp b_cj, b_ci, b_stage, b_y;
-  if (own_c) RET(b_cj.alloc((size_t)ns * ov));
-  if (own_c && ns < N) RET(b_ci.alloc((size_t)ns * ov));
-  if (host && blocks) RET(b_stage.alloc((size_t)ns * dim));
-  RET(b_y.alloc((size_t)X * ns * ov));
+  TmpBuf b_cj, b_ci, b_stage, b_y;
+  if (own_c) RET(b_cj.ensure((size_t)ns * ov, what));
+  if (own_c && ns < N) RET(b_ci.ensure((size_t)ns * ov, what));
+  if (host && blocks) RET(b_stage.ensure((size_t)ns * dim, what));
+  RET(b_y.ensure((size_t)X * ns * ov, what));
   auto load_chunk = [&](long s0, long n, double* buf, const double** c) -> int {
     const double* src = vecs + s0 * dim;
     if (host) {
       double* dst = blocks ? b_stage.p : buf;
-      HIPCHK(hipMemcpyAsync(dst, src, (size_t)n * dim * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(what, hipMemcpyAsync(dst, src, (size_t)n * dim * 8, hipMemcpyHostToDevice, st));
       src = dst;
     }
     if (blocks) {
@@ -334,8 +294,8 @@ extern "C" int xt_tdm(const xt_tdm_desc* desc, const double* op_ao, const double
       RET(run(g));
     }
   }
-  HIPCHK(hipGetLastError());
-  if (host) HIPCHK(hipMemcpyAsync(out, outd, (size_t)X * N * N * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));   // the workspace is released on return
+  HIPCHK(what, hipGetLastError());
+  if (host) HIPCHK(what, hipMemcpyAsync(out, outd, (size_t)X * N * N * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(what, hipStreamSynchronize(st));   // the workspace is released on return
   return 0;
 }

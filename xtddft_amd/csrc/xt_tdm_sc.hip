@@ -26,10 +26,7 @@
 // plans and with them the bits repeat.  No atomics anywhere.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
-#include <string>
-#include "../../include/xtddft_amd.h"
-#include "xt_internal.h"
+#include "xt_host.h"
 
 using namespace xt;
 
@@ -83,25 +80,7 @@ __global__ void k_sc_ground(int ncomp, int nstates, const double* __restrict__ g
   }
 }
 
-// call-scoped device memory: released on every return path
-struct Tmp {
-  double* p = nullptr;
-  size_t n = 0;
-  ~Tmp() { if (p) (void)hipFree(p); }
-  int alloc(size_t count) {
-    if (count == 0) return 0;
-    if (hipMalloc(&p, count * sizeof(double)) != hipSuccess) {
-      p = nullptr;
-      return set_error(XT_ERR_OOM, ("xt_tdm_sc: hipMalloc failed for " + std::to_string(count * 8) + " bytes").c_str());
-    }
-    n = count;
-    return 0;
-  }
-};
-
-#define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) \
-    return set_error(XT_ERR_HIP, (std::string("xt_tdm_sc: " #x ": ") + hipGetErrorString(_e)).c_str()); } while (0)
-#define RET(x) do { int _r = (x); if (_r) return _r; } while (0)
+const char* const what = "xt_tdm_sc";   // message prefix
 
 }  // namespace
 
@@ -143,58 +122,39 @@ extern "C" int xt_tdm_sc(const xt_tdm_sc_desc* desc, const double* op_ao, const 
   const double h = corr ? sqrt((d.si + 1.0) / (2.0 * d.si)) - M_SQRT1_2 : 0.0;
 
   // states per chunk: Y for every component, the two uploaded chunks, cv1 and Ycv1 within
-  // the budget (XT_TDM_WS_MIB, default 768: a tuning hook, and how the tests reach the
-  // chunked path at small sizes)
-  double budget = 768.0;
-  if (const char* e = getenv("XT_TDM_WS_MIB")) { const double v = atof(e); if (v > 0.0 && v < 768.0) budget = v; }
+  // the budget (tdm_budget_mib)
   const double per_state = 8.0 * ((double)(X + 2) * dim + (double)(X + 1) * cv);
-  long ns = (long)(budget * 1048576.0 / per_state);
+  long ns = (long)(tdm_budget_mib() * 1048576.0 / per_state);
   if (ns > 32768 / X) ns = 32768 / X;   // (state, component) batches of one launch: grid z
   ns = ns < 1 ? 1 : (ns > N ? N : ns);
   if ((long)X * ns > 32768) return set_error(XT_ERR_ARG, "xt_tdm_sc: ncomp > 32768");
 
   // ---- inputs on the device ----
-  Tmp b_op, b_coa, b_cva, b_cob, b_cvb, b_out;
-  auto upload = [&](Tmp& b, const double*& p, size_t count) -> int {
-    if (!host || !p || count == 0) return 0;
-    RET(b.alloc(count));
-    HIPCHK(hipMemcpyAsync(b.p, p, count * 8, hipMemcpyHostToDevice, st));
-    p = b.p;
-    return 0;
-  };
-  RET(upload(b_op, op_ao, (size_t)X * nao * nao));
-  RET(upload(b_coa, c_occ_a, (size_t)nao * Oa));
-  RET(upload(b_cva, c_vir_a, (size_t)nao * Va));
-  RET(upload(b_cob, c_occ_b, (size_t)nao * Ob));
-  RET(upload(b_cvb, c_vir_b, (size_t)nao * Vb));
+  TmpBuf b_op, b_coa, b_cva, b_cob, b_cvb, b_out;
+  RET(upload(b_op, op_ao, (size_t)X * nao * nao, ptr_kind, st, what));
+  RET(upload(b_coa, c_occ_a, (size_t)nao * Oa, ptr_kind, st, what));
+  RET(upload(b_cva, c_vir_a, (size_t)nao * Va, ptr_kind, st, what));
+  RET(upload(b_cob, c_occ_b, (size_t)nao * Ob, ptr_kind, st, what));
+  RET(upload(b_cvb, c_vir_b, (size_t)nao * Vb, ptr_kind, st, what));
   double* outd = out;
-  if (host) { RET(b_out.alloc((size_t)X * N1 * N1)); outd = b_out.p; }
+  if (host) { RET(b_out.ensure((size_t)X * N1 * N1, what)); outd = b_out.p; }
 
-  // ---- engine launches (split-K workspace grown on demand) ----
-  Tmp ws;
+  // ---- engine launches (split-K workspace grown on demand, 256 MiB cap) ----
+  TmpBuf ws;
   auto run = [&](const GemmDesc& g) -> int {
     if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.nb1 <= 0 || g.nb2 <= 0) return 0;   // empty block: nothing is launched
-    size_t need = dgemm_workspace_bytes(g);
-    const size_t cap = (size_t)256 << 20;
-    if (need > cap) need = cap;
-    if (need > ws.n * 8) {
-      HIPCHK(hipStreamSynchronize(st));   // an earlier product may still reduce from it
-      if (ws.p) { (void)hipFree(ws.p); ws.p = nullptr; ws.n = 0; }
-      RET(ws.alloc(need / 8 + 1));
-    }
-    const int r = dgemm(g, st, ws.p, ws.n * 8);
-    return r ? set_error(r, "xt_tdm_sc: GEMM launch failed") : 0;
+    return run_gemm(g, st, ws, (size_t)256 << 20, 0, what, "GEMM launch failed");
   };
 
   // ---- d_oo, d_vv per spin and component; d_ov straight into the ground image ----
   const int oab = Oa > Ob ? Oa : Ob, vab = Va > Vb ? Va : Vb;
-  Tmp b_half, b_doa, b_dva, b_dob, b_dvb, b_img, b_g;
-  RET(b_half.alloc((size_t)X * nao * (oab > vab ? oab : vab)));
-  RET(b_doa.alloc((size_t)X * Oa * Oa));
-  RET(b_dva.alloc((size_t)X * Va * Va));
-  RET(b_dob.alloc((size_t)X * Ob * Ob));
-  RET(b_dvb.alloc((size_t)X * Vb * Vb));
-  if (G) { RET(b_img.alloc((size_t)X * dim)); RET(b_g.alloc((size_t)X * N)); }
+  TmpBuf b_half, b_doa, b_dva, b_dob, b_dvb, b_img, b_g;
+  RET(b_half.ensure((size_t)X * nao * (oab > vab ? oab : vab), what));
+  RET(b_doa.ensure((size_t)X * Oa * Oa, what));
+  RET(b_dva.ensure((size_t)X * Va * Va, what));
+  RET(b_dob.ensure((size_t)X * Ob * Ob, what));
+  RET(b_dvb.ensure((size_t)X * Vb * Vb, what));
+  if (G) { RET(b_img.ensure((size_t)X * dim, what)); RET(b_g.ensure((size_t)X * N, what)); }
   auto half = [&](const double* cm, int n) -> int {   // half[x] = op[x] C
     GemmDesc g;
     g.M = nao; g.N = n; g.K = nao; g.nb1 = X;
@@ -224,15 +184,15 @@ extern "C" int xt_tdm_sc(const xt_tdm_sc_desc* desc, const double* op_ao, const 
   RET(spin_blocks(c_occ_b, c_vir_b, Ob, Vb, b_dob.p, b_dvb.p, na));
 
   // ---- state chunks ----
-  Tmp b_zj, b_zi, b_y, b_cv1, b_ycv1;
-  if (host) RET(b_zj.alloc((size_t)ns * dim));
-  if (host && ns < N) RET(b_zi.alloc((size_t)ns * dim));
-  RET(b_y.alloc((size_t)X * ns * dim));
-  if (corr) { RET(b_cv1.alloc((size_t)ns * cv)); RET(b_ycv1.alloc((size_t)X * ns * cv)); }
+  TmpBuf b_zj, b_zi, b_y, b_cv1, b_ycv1;
+  if (host) RET(b_zj.ensure((size_t)ns * dim, what));
+  if (host && ns < N) RET(b_zi.ensure((size_t)ns * dim, what));
+  RET(b_y.ensure((size_t)X * ns * dim, what));
+  if (corr) { RET(b_cv1.ensure((size_t)ns * cv, what)); RET(b_ycv1.ensure((size_t)X * ns * cv, what)); }
   auto load_chunk = [&](long s0, long n, double* buf, const double** z) -> int {
     const double* src = vecs + s0 * dim;
     if (host) {
-      HIPCHK(hipMemcpyAsync(buf, src, (size_t)n * dim * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(what, hipMemcpyAsync(buf, src, (size_t)n * dim * 8, hipMemcpyHostToDevice, st));
       src = buf;
     }
     *z = src;
@@ -322,8 +282,8 @@ extern "C" int xt_tdm_sc(const xt_tdm_sc_desc* desc, const double* op_ao, const 
   }
   if (G)
     hipLaunchKernelGGL(k_sc_ground, dim3(nblocks((long)X * N1)), dim3(256), 0, st, X, N, b_g.p, outd);
-  HIPCHK(hipGetLastError());
-  if (host) HIPCHK(hipMemcpyAsync(out, outd, (size_t)X * N1 * N1 * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));   // the workspace is released on return
+  HIPCHK(what, hipGetLastError());
+  if (host) HIPCHK(what, hipMemcpyAsync(out, outd, (size_t)X * N1 * N1 * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(what, hipStreamSynchronize(st));   // the workspace is released on return
   return 0;
 }
