@@ -328,6 +328,48 @@ int xt_tdm_sc(const xt_tdm_sc_desc* desc, const double* op_ao, const double* c_o
               const double* c_occ_b, const double* c_vir_b, const double* vecs, double* out, int ptr_kind,
               void* hip_stream);
 
+/* Spin-orbit state interaction: the bilinear couplings of a real one-electron operator in the
+   MO basis [c|o|v] between the roots of the three TDA manifolds of a high-spin ROKS reference
+   and the reference state itself (SI_driver.make_hso_local / make_dm_local,
+   x2c_hamiltonian/driver/si_driver.py:472-916; the 61 cases of si_driver.py:520-867 and the
+   tables of x2c_hamiltonian/driver/tdm.py).  Groups in the order of the reference's H_eff,
+   |S->, |GS>, |So>, |S+>; out[x][L][R], (ncomp, n, n), n = n_sm + with_ground + n_so + n_sp.
+   State vectors in the reference's layouts, row-major blocks:
+     |S->  [CV(1) nc x nv | CO(1) nc x no | OV(1) no x nv | O1O2 no x no | O1O1 no]
+     |So>  [CV(0) nc x nv | CO(0) nc x no | OV(0) no x nv | CV(1) nc x nv]
+     |S+>  CV(1) nc x nv
+   XT_SI_SOC: op antisymmetric; the rank-1 tables interact_S_1S_1, _S_1GS, _S_1S, _GSS, _GSS1,
+   _SS, _SS1, _S1S1 with hm replaced by the real component op[x] (every term is linear in hm
+   with a real factor; the host forms h^m from the components).  Every same-manifold square
+   block is filled in full, the other blocks with L before R in the group order; S-/S+, GS/GS
+   and the blocks below the diagonal are zeros.  The CV(1) cases 45, 50, 54, 57, 59, 60 apply
+   with S != 0 only.
+   XT_SI_DIPOLE: op symmetric; the same-S blocks S-/S- (TDM_S_1), GS/So (TDM_GSS), So/So (TDM_S,
+   with tdm.py's CV(1) phase: +sqrt((S+1)/(2S)), the opposite of utils.so2st) and S+/S+
+   (TDM_S1); all else zeros.
+   Arguments are validated before any HIP call (XT_ERR_ARG: negative counts, no state at all,
+   s != no / 2, |S-> states with S < 1, a bad mode, with_ground or ptr_kind, null pointers
+   where there is work, nmo or a vector length >= 2^21).  Every term is an engine GEMM on a
+   block of op addressed in place by its strides; the O1O1 terms, the reference-state images
+   and their placement are small kernels; one Gram product over the vector dimension per pair
+   of groups.  No atomics, fixed-order reductions: two calls on the same input return the
+   same bits.  The workspace lives for the call; the part that grows with the number of
+   states is capped as in xt_tdm_sc (XT_TDM_WS_MIB; states are processed in chunks). */
+#define XT_SI_SOC 0
+#define XT_SI_DIPOLE 1
+typedef struct xt_si_desc {
+  int nc, no, nv;         /* nmo = nc + no + nv */
+  int ncomp;              /* operator components (3) */
+  double s;               /* S of the reference, = no / 2 */
+  int n_sm, n_so, n_sp;   /* states of |S->, |So>, |S+> */
+  int with_ground;        /* 1: the reference state is a group of one */
+  int mode;               /* XT_SI_SOC / XT_SI_DIPOLE */
+} xt_si_desc;
+/* op_mo (ncomp, nmo, nmo); x_sm (n_sm, dim_sm), x_so (n_so, dim_so), x_sp (n_sp, nc nv)
+   row-major (an empty group may be null); out (ncomp, n, n).  All pointers of one ptr_kind. */
+int xt_si_couple(const xt_si_desc* desc, const double* op_mo, const double* x_sm, const double* x_so,
+                 const double* x_sp, double* out, int ptr_kind, void* hip_stream);
+
 /* VV10 non-local correlation on a quadrature grid: the pair sums behind the response term
    the reference takes from pyscf.hessian.rks.get_vnlc_resp (XTDA.py:515-517).  The energy is
      E = sum_i a_i [beta + 1/2 sum_j a_j Phi_ij],  a_i = w_i rho_i,  j = i included,

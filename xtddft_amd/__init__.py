@@ -8,6 +8,8 @@ Reference-compatible entry points (PySCF-style operator API):
 * ``XSF_TDA(mf, SA, ...)``              (xtddft/XSF_TDA.py)
 * ``davidson1``                         (xtddft/utils/Davidson.py)
 * ``OSsTDA(mol, mf, ...)``              (xtddft/sTDA/os_sTDA.py)
+* ``SI_driver(mf, S, Vso, ...)``        (x2c_hamiltonian/driver/si_driver.py) and the
+  ``states_from_xsf`` / ``states_from_xtda`` / ``states_from_sf_up`` helpers
 
 The arithmetic runs in the HIP library ``_lib/libxtddft_amd.so`` (C ABI in
 ``include/xtddft_amd.h``); there is no CPU fallback.
@@ -16,7 +18,8 @@ from .meanfield import Grid, MeanField, Mole
 from .utils import HA2EV, HA2EV_XSF, order_pyscf2my, so2st, st2so
 
 __all__ = ["Grid", "MeanField", "Mole", "HA2EV", "HA2EV_XSF", "order_pyscf2my", "so2st", "st2so",
-           "XTDA", "SF_TDA", "SF_TDA_up", "SF_TDA_down", "XSF_TDA", "davidson1", "DeviceOperator", "OSsTDA"]
+           "XTDA", "SF_TDA", "SF_TDA_up", "SF_TDA_down", "XSF_TDA", "davidson1", "DeviceOperator", "OSsTDA",
+           "SI_driver", "si_couple", "states_from_xsf", "states_from_xtda", "states_from_sf_up"]
 
 
 def __getattr__(name):   # lazy: importing the package must not require a GPU
@@ -35,6 +38,9 @@ def __getattr__(name):   # lazy: importing the package must not require a GPU
     if name == "OSsTDA":
         from .stda import OSsTDA
         return OSsTDA
+    if name in ("SI_driver", "si_couple", "states_from_xsf", "states_from_xtda", "states_from_sf_up"):
+        from . import soc
+        return getattr(soc, name)
     if name == "DeviceOperator":
         from .operator import DeviceOperator
         return DeviceOperator

@@ -33,6 +33,7 @@ EXPORTS = [
     "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao", "xt_tdm", "xt_tdm_sc", "xt_gemm_plan", "xt_gemm_run",
     "xt_set_nlc", "xt_vv10_ground", "xt_vv10_response",
     "xt_stda_charges", "xt_stda_half", "xt_stda_diag", "xt_stda_select", "xt_stda_matrix",
+    "xt_si_couple",
 ]
 
 
@@ -61,6 +62,17 @@ class XtTdmScDesc(ctypes.Structure):
         ("nao", c_int), ("nocc_a", c_int), ("nvir_a", c_int), ("nocc_b", c_int), ("nvir_b", c_int),
         ("ncomp", c_int), ("nstates", c_int), ("spin_adapted", c_int), ("no", c_int), ("si", c_double),
         ("with_ground", c_int),
+    ]
+
+
+SI_MODE = {"soc": 0, "dipole": 1}   # XT_SI_*
+
+
+class XtSiDesc(ctypes.Structure):
+    """xt_si_desc: orbital and state counts of the state-interaction couplings."""
+    _fields_ = [
+        ("nc", c_int), ("no", c_int), ("nv", c_int), ("ncomp", c_int), ("s", c_double),
+        ("n_sm", c_int), ("n_so", c_int), ("n_sp", c_int), ("with_ground", c_int), ("mode", c_int),
     ]
 
 
@@ -161,6 +173,7 @@ def lib():
     L.xt_eval_ao.argtypes = [c_int, dp, c_int, vp, dp, dp, dp, c_int, dp, c_long, c_long, vp]
     L.xt_tdm.argtypes = [POINTER(XtTdmDesc), dp, dp, dp, dp, dp, dp, c_int, vp]
     L.xt_tdm_sc.argtypes = [POINTER(XtTdmScDesc), dp, dp, dp, dp, dp, dp, dp, c_int, vp]
+    L.xt_si_couple.argtypes = [POINTER(XtSiDesc), dp, dp, dp, dp, dp, c_int, vp]
     pi = POINTER(c_int)
     L.xt_gemm_plan.argtypes = [POINTER(XtGemmDesc), pi, pi, pi, pi, pi, pi]
     L.xt_gemm_run.argtypes = [POINTER(XtGemmDesc), dp, dp, dp, vp]
