@@ -516,6 +516,28 @@ int xt_int2e_cart(int npair, const int* pair_info, const double* pair_prim, cons
                   int nket, const int* ket_info, const double* ket_prim, const double* ek,
                   int lmax_orb, int lket, double omega, const double* q_bra, const double* q_ket,
                   double q_thr, int diag, double* out, long ldo, void* hip_stream);
+/* Coulomb integrals between charge distributions given directly as Hermite expansions: the
+   derivative integrals of the spin-orbit mean field (the reference's sfX2C_soDKH1.py get_kint,
+   get_wso and int1e_pnucp; xtddft_amd/qc/ints.py deriv_tables builds the tables).  As
+   xt_int2e_cart, but every table entry states its Hermite order and its number of rows:
+     bra_info[8k+0..6]   order, nrow, npp, first row of bra_prim, offset in eb, first output row, tag
+     bra_prim[4q+0..3]   p, Px, Py, Pz of primitive pair q
+     eb                  per entry [row][t][q] over nrow x ntuv(order) x npp
+     ket_info[8j+0..6]   order, nprim, first row of ket_prim, offset in ek, first output column, ncol, tag
+     ket_prim[4r+0..3]   exponent, Cx, Cy, Cz
+     ek                  per entry [col][u][r] over ncol x ntuv(order) x nprim
+   cross = 0: out[(row0 + row) * ldo + col0 + col] += (row|col).
+   cross = 1: rows are (m, ab) and columns (n, cd) with m, n = x, y, z outermost (nrow = 3 nab,
+   ncol = 3 ncd; row0 / col0 count ab / cd); the three cross products are written directly,
+     out[(l * nrow_tot + row0 + ab) * ldo + col0 + cd] += eps_lmn ((m, ab)|(n, cd)),
+   and the m = n products are never formed.  `out` is accumulated into (zero it first); blocks
+   of different (bra, ket) entries must not overlap.  A (bra, ket) pair whose tags differ is
+   skipped (the one-centre approximation: tag = atom; 0 everywhere computes every pair).  lbra / lket bound the orders of the two
+   tables: lbra <= 8, lbra + lket <= 14.  The tables are device memory and are not read on the
+   host; an entry whose order exceeds the declared bounds is skipped (its block stays zero). */
+int xt_hint_cart(int nbra, const int* bra_info, const double* bra_prim, const double* eb,
+                 int nket, const int* ket_info, const double* ket_prim, const double* ek,
+                 int lbra, int lket, int cross, long nrow_tot, double* out, long ldo, void* hip_stream);
 /* AO values (deriv 0) or values and gradients (deriv 1) of normalised spherical
    AOs on grid points (PySCF mol.eval_ao / ni.block_loop, SF_TDA.py:63-68, the AO
    input of cache_xc_kernel / nr_uks_fxc, XTDA.py:504,514), device pointers:

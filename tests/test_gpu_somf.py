@@ -1,0 +1,372 @@
+"""GPU: the Hermite-form Coulomb kernel ``xt_hint_cart`` (xtddft_amd/csrc/xt_hint.hip), the
+semi-direct spin-orbit mean-field contraction built on it (``qc.dints.somf_g_device``,
+``int1e_pvp_device``) and the chain get_soDKH1_somf -> vso_mo -> SI_driver.
+
+Kernel bound, elementwise, as tests/test_gpu_int_paths.py holds xt_int2e_cart to:
+|dev - ref| <= kappa(L) 2^-53 sabs, with ref and sabs (the same sum over the absolute values of
+every factor) from the 40-digit machinery of tests/int_ref.py (``ref_hint`` below generalises
+``ref_int2e`` to stated orders, row counts and the cross mode) and kappa(L) the stored figure of
+tests/golden/int_ref.npz (8 x the host's error at total order L, floor 64).  The fixture stops
+at L = 13; L = 14, reached only by (d f  f|d f  f), takes the largest stored kappa: the figure
+does not grow with L (it is 64 at most orders), and the extra order adds one recursion level.
+
+Classes (la, lb|lc, ld): every l in {0, 1, 2, 3} occurs at every one of the four positions (the
+four cyclic shifts of (0, 1, 2, 3)), plus the uniform classes (ss|ss) .. (ff|ff) and single
+high-l shells; 1 and 3 primitives; four distinct centres and two coincident centres.
+
+Contraction bound: 1e-12 of the largest element against the host restatement (the project's
+device = host bar), chunked against unchunked 1e-13, two calls the same bits.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+import int_cases as ic
+import int_ref
+import si_ref
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = -7777.25
+GUARD = 64
+U = 2.0 ** -53
+
+CENTRES = np.array([[0.0, 0.0, 0.0], [0.9, -0.4, 0.3], [-0.5, 0.7, 1.1], [0.2, 1.3, -0.8]])
+# (la, lb, lc, ld), primitives per shell, centre of each shell
+CASES = [
+    ((0, 0, 0, 0), (3, 1, 1, 3), (0, 1, 2, 3)),
+    ((1, 1, 1, 1), (1, 3, 3, 1), (0, 1, 2, 3)),
+    ((2, 2, 2, 2), (1, 1, 3, 1), (0, 1, 0, 2)),
+    ((3, 3, 3, 3), (1, 1, 1, 1), (0, 1, 2, 3)),
+    ((3, 3, 3, 3), (1, 1, 1, 1), (0, 0, 1, 2)),
+    ((0, 1, 2, 3), (3, 1, 3, 1), (0, 1, 2, 3)),
+    ((1, 2, 3, 0), (1, 3, 1, 3), (0, 1, 2, 3)),
+    ((2, 3, 0, 1), (3, 1, 1, 3), (1, 1, 2, 3)),
+    ((3, 0, 1, 2), (1, 3, 1, 1), (0, 1, 2, 2)),
+    ((3, 0, 0, 0), (3, 3, 1, 1), (0, 1, 2, 3)),
+    ((0, 0, 0, 3), (1, 1, 3, 3), (0, 0, 1, 1)),
+]
+IDS = ["".join("spdf"[l] for l in c[0]) + "-n" + "".join(map(str, c[1])) + "-c" + "".join(map(str, c[2])) for c in CASES]
+
+
+@pytest.fixture(scope="module")
+def torch(hiplib):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch
+
+
+@pytest.fixture(scope="module")
+def kappa():
+    k = ic.load_fixture()["kappa"]
+    return np.concatenate([k, [k.max()] * (15 - len(k))])
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int64)
+
+
+def shell(l, nprim, centre, seed):
+    from xtddft_amd.qc.gto import Shell, gto_norm
+    rng = np.random.default_rng(seed)
+    exps = 0.4 * 3.1 ** np.arange(nprim) * (1.0 + 0.3 * rng.random(nprim))
+    coefs = (0.5 + rng.random(nprim)) * gto_norm(l, exps)
+    return Shell(int(centre), l, CENTRES[centre].copy(), exps, coefs)
+
+
+def tables(pairs, unit):
+    """xt_hint_cart tables of DerivPair entries; a pair's output offset advances by unit * nab
+    (unit 3: plain mode, its rows are (m, a, b); unit 1: cross mode)."""
+    from xtddft_amd.qc.ints import DerivPair
+    info, prim, e = [], [], []
+    q0 = e0 = o0 = 0
+    for sa, sb in pairs:
+        dp = DerivPair(sa, sb)
+        tab = dp.Eab[:, 0]
+        info.append([dp.L, tab.shape[0], dp.p.size, q0, e0, o0, 0, 0])
+        prim.append(np.column_stack([dp.p, dp.P]))
+        e.append(tab.ravel())
+        q0 += dp.p.size
+        e0 += tab.size
+        o0 += unit * dp.nab
+    return np.array(info, dtype=np.int32), np.concatenate(prim), np.concatenate(e), o0
+
+
+def as_ket(info):
+    """bra rows (order, nrow, npp, prim0, e0, row0) -> ket rows (order, nprim, prim0, e0, col0, ncol)."""
+    out = np.zeros_like(info)
+    out[:, 0], out[:, 1:4], out[:, 4], out[:, 5] = info[:, 0], info[:, 2:5], info[:, 5], info[:, 1]
+    return out
+
+
+def ref_hint(binfo, bprim, eb, kinfo, kprim, ek, cross, nrow_tot, ldo):
+    """int_ref.ref_int2e for xt_hint_cart: orders and row counts read from the tables, and in
+    cross mode the eps_lmn combination of the (m | n) blocks.  (ref, sabs, L) of shape
+    (ncomp, nrow_tot, ldo), ncomp = 3 (cross) or 1."""
+    import mpmath as mp
+    LD, WIDE = int_ref.LD, int_ref.WIDE
+    ncomp = 3 if cross else 1
+    zero = LD(0) if WIDE else mp.mpf(0)
+    ref = np.full((ncomp, nrow_tot, ldo), zero, dtype=LD if WIDE else object)
+    sab = ref.copy()
+    Lmap = np.full((ncomp, nrow_tot, ldo), -1, dtype=np.int64)
+    bprim, kprim = np.asarray(bprim).reshape(-1, 4), np.asarray(kprim).reshape(-1, 4)
+    with mp.workdps(int_ref.DPS):
+        for j in range(len(kinfo)):
+            for k in range(len(binfo)):
+                lb, nrow, npp, bq0, be0, row0 = (int(x) for x in binfo[k][:6])
+                lk, nr, kr0, ke0, col0, ncol = (int(x) for x in kinfo[j][:6])
+                L, nt, nu = lb + lk, int_ref.ntuv(lb), int_ref.ntuv(lk)
+                E = int_ref._wide_array(np.asarray(eb[be0:be0 + nrow * nt * npp]).reshape(nrow, nt, npp))
+                K = int_ref._wide_array(np.asarray(ek[ke0:ke0 + ncol * nu * nr]).reshape(ncol, nu, nr))
+                idx, sign = int_ref._sum_index(lb, lk)
+                Ks = K * (sign[None, :, None].astype(LD) if WIDE else sign[None, :, None].astype(int).astype(object))
+                blk = np.full((nrow, ncol), zero, dtype=ref.dtype)
+                blka = blk.copy()
+                for q in range(npp):
+                    p = mp.mpf(float(bprim[bq0 + q, 0]))
+                    P = [mp.mpf(float(x)) for x in bprim[bq0 + q, 1:]]
+                    for r in range(nr):
+                        s = mp.mpf(float(kprim[kr0 + r, 0]))
+                        C = [mp.mpf(float(x)) for x in kprim[kr0 + r, 1:]]
+                        Rt = int_ref.hermite_r_mp(L, p * s / (p + s), P[0] - C[0], P[1] - C[1], P[2] - C[2])
+                        pref = int_ref._wide(2 * mp.pi ** 2.5 / (p * s * mp.sqrt(p + s)))
+                        Rg = np.array([int_ref._wide(x) for x in Rt], dtype=ref.dtype)[idx]
+                        blk += pref * (E[:, :, q] @ (Rg @ Ks[:, :, r].T))
+                        blka += abs(pref) * (np.abs(E[:, :, q]) @ (np.abs(Rg) @ np.abs(K[:, :, r]).T))
+                if not cross:
+                    ref[0, row0:row0 + nrow, col0:col0 + ncol] = blk
+                    sab[0, row0:row0 + nrow, col0:col0 + ncol] = blka
+                    Lmap[0, row0:row0 + nrow, col0:col0 + ncol] = L
+                    continue
+                nab, ncd = nrow // 3, ncol // 3
+                b4 = blk.reshape(3, nab, 3, ncd)
+                a4 = blka.reshape(3, nab, 3, ncd)
+                for l, m, n in ((0, 1, 2), (1, 2, 0), (2, 0, 1)):
+                    ref[l, row0:row0 + nab, col0:col0 + ncd] = b4[m, :, n] - b4[n, :, m]
+                    sab[l, row0:row0 + nab, col0:col0 + ncd] = a4[m, :, n] + a4[n, :, m]
+                    Lmap[l, row0:row0 + nab, col0:col0 + ncd] = L
+
+    def f64(a):
+        return a.astype(np.float64) if WIDE else np.array([float(x) for x in a.ravel()]).reshape(a.shape)
+    return f64(ref), f64(sab), Lmap
+
+
+def launch(torch, hiplib, bra, ket, cross, nrow_tot, ldo):
+    """One xt_hint_cart call: NaN slack behind every table, `out` between sentinel guards."""
+    ncomp = 3 if cross else 1
+
+    def up(a):
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.float64:
+            a = np.concatenate([a.ravel(), np.full(GUARD, np.nan)])
+        return torch.from_numpy(a).cuda()
+    dev = [up(x) for x in (*bra, *ket)]
+    flat = np.concatenate([np.full(GUARD, SENTINEL), np.zeros(ncomp * nrow_tot * ldo), np.full(GUARD, SENTINEL)])
+    d_out = torch.from_numpy(flat).cuda()
+    lbra, lket = int(bra[0][:, 0].max()), int(ket[0][:, 0].max())
+    rc = hiplib.xt_hint_cart(len(bra[0]), *[x.data_ptr() for x in dev[:3]], len(ket[0]),
+                             *[x.data_ptr() for x in dev[3:]], lbra, lket, int(cross), nrow_tot,
+                             d_out.data_ptr() + 8 * GUARD, ldo,
+                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    got = d_out.cpu().numpy()
+    assert rc == 0
+    assert np.array_equal(_bits(got[:GUARD]), _bits(flat[:GUARD])), "write before out"
+    assert np.array_equal(_bits(got[-GUARD:]), _bits(flat[-GUARD:])), "write past out"
+    return got[GUARD:-GUARD].reshape(ncomp, nrow_tot, ldo)
+
+
+def check(tag, out, ref, sabs, Lmap, kappa):
+    m = Lmap >= 0
+    assert np.all(out[~m] == 0.0), "output outside the blocks was touched"
+    bound = kappa[np.maximum(Lmap, 0)] * U * sabs
+    err = np.abs(out - ref)
+    live = m & (bound > 0)
+    worst = float((err[live] / bound[live]).max())
+    print(f"HINTRATIO {tag} L={int(Lmap.max())} worst |dev - ref| / bound {worst:.4f}, max|ref| {np.abs(ref).max():.3e}")
+    assert np.all(np.isfinite(out)) and np.any(ref[m] != 0.0)
+    assert np.all(out[m & (sabs == 0)] == 0.0)
+    assert np.all(err[m] <= bound[m]), (tag, worst)
+
+
+def run_both_modes(torch, hiplib, kappa, tag, bra_pairs, ket_pairs):
+    for cross, unit in ((0, 3), (1, 1)):
+        bi, bp, be, nrow = tables(bra_pairs, unit)
+        ki, kp, ke, ncol = tables(ket_pairs, unit)
+        ki = as_ket(ki)
+        out = launch(torch, hiplib, (bi, bp, be), (ki, kp, ke), cross, nrow, ncol)
+        check(f"{tag} {'cross' if cross else 'plain'}", out, *ref_hint(bi, bp, be, ki, kp, ke, cross, nrow, ncol), kappa)
+
+
+# --------------------------------------------------------------------------- the kernel
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_kernel_class_against_40_digits(torch, hiplib, kappa, case):
+    ls, nps, cs = case
+    sh = [shell(l, n, c, 10 * i + l) for i, (l, n, c) in enumerate(zip(ls, nps, cs))]
+    run_both_modes(torch, hiplib, kappa, "(%d%d|%d%d)" % ls, [(sh[0], sh[1])], [(sh[2], sh[3])])
+
+
+def test_kernel_partial_wave_and_single_ket(torch, hiplib, kappa):
+    """9 ordered pairs of three s / p shells against themselves: 81 quartets, a full wave and a
+    partial one of mixed classes; and the same bras against one ket."""
+    sh = [shell(0, 2, 0, 1), shell(1, 1, 1, 2), shell(1, 2, 3, 3)]
+    pairs = [(a, b) for a in sh for b in sh]
+    order = sorted(range(9), key=lambda k: pairs[k][0].l + pairs[k][1].l)
+    pairs = [pairs[k] for k in order]
+    run_both_modes(torch, hiplib, kappa, "81 quartets", pairs, pairs)
+    run_both_modes(torch, hiplib, kappa, "1 ket", pairs, [pairs[4]])
+
+
+# --------------------------------------------------------------------------- the contraction
+def f_basis():
+    return {"F": [[0, [9.1, 0.4], [1.3, 0.7]], [1, [2.2, 1.0]], [3, [1.1, 1.0]]],
+            "H": [[0, [1.2, 0.6], [0.3, 0.5]], [1, [0.8, 1.0]]]}
+
+
+MOLS = {
+    "HF-631G": dict(atom="F 0 0 0; H 0 0 1.0", basis="6-31G"),
+    "OH-ccpvdz": dict(atom="O 0 0 0; H 0.3 -0.2 0.95", basis="cc-pvdz", spin=1),
+    "FH-f": dict(atom="F 0 0 0; H 0.2 0.1 0.9", basis=f_basis()),
+}
+_HOST = {}
+
+
+def host(name):
+    """Molecule, densities and the host restatement (full and one-centre), once per molecule."""
+    if name not in _HOST:
+        from xtddft_amd import somf
+        from xtddft_amd.qc import M
+        mol = M(**MOLS[name])
+        n = mol.nao
+        rng = np.random.default_rng(5)
+        a, b, c = (rng.standard_normal((n, n)) for _ in range(3))
+        p = dict(pLL=a + a.T, pLS=b, pSS=c + c.T)
+        K = somf.kint_host(mol)
+        at = mol.ao_atom()
+        same = (at[:, None, None, None] == at[None, :, None, None]) & (at[:, None, None, None] == at[None, None, :, None]) \
+            & (at[:, None, None, None] == at[None, None, None, :])
+        want = {False: somf.somf_g_host(mol, **p, kint=K), True: somf.somf_g_host(mol, **p, kint=K * same[None])}
+        for x in (*p.values(), *want[False], *want[True]):
+            x.setflags(write=False)
+        _HOST[name] = dict(mol=mol, p=p, want=want, pvp=mol._pvp())
+    return _HOST[name]
+
+
+def relerr(got, want):
+    return max(np.abs(g - w).max() / np.abs(w).max() for g, w in zip(got, want))
+
+
+@pytest.mark.parametrize("use_1c", [False, True], ids=["full", "1c"])
+@pytest.mark.parametrize("name", list(MOLS))
+def test_contraction_matches_the_host(torch, name, use_1c):
+    from xtddft_amd.qc.dints import deriv_pair_table, somf_g_device
+    h = host(name)
+    mol, p = h["mol"], h["p"]
+    whole = somf_g_device(mol, **p, use_1c=use_1c)
+    err = relerr(whole, h["want"][use_1c])
+    npair = deriv_pair_table(mol, use_1c).npair
+    print(f"{name} 1c={use_1c}: {npair} pairs, device vs host {err:.2e}")
+    assert err < 1e-12
+    again = somf_g_device(mol, **p, use_1c=use_1c)
+    assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(whole, again))
+    chunks = (1, 7, npair) if name == "HF-631G" else (7,)        # 7 divides neither 81 nor the one-centre counts
+    for chunk in chunks:
+        got = somf_g_device(mol, **p, use_1c=use_1c, chunk_pairs=chunk)
+        split = relerr(got, whole)
+        print(f"  chunk {chunk}: vs unchunked {split:.2e}")
+        assert split < 1e-13 and relerr(got, h["want"][use_1c]) < 1e-12
+
+
+@pytest.mark.parametrize("name", list(MOLS))
+def test_one_electron_integrals_match_the_host(torch, name):
+    from xtddft_amd.qc.dints import int1e_pvp_device
+    h = host(name)
+    got = int1e_pvp_device(h["mol"])
+    want = h["pvp"]
+    for c in range(4):
+        err = np.abs(got[c] - want[c]).max() / np.abs(want[c]).max()
+        print(f"{name} pvp component {c}: {err:.2e}")
+        assert err < 1e-12
+    assert np.array_equal(_bits(got), _bits(int1e_pvp_device(h["mol"])))
+    assert np.array_equal(got[0], h["mol"].intor("int1e_pnucp", device=0))
+
+
+# --------------------------------------------------------------------------- nothing else moved
+def test_existing_integrals_keep_their_bits(torch, hiplib):
+    """eri_full_device and int1e_nuc_device before and after launches of the new kernel, and
+    the Cartesian stage of eri_full_device against a direct call of the unchanged xt_int2e_cart."""
+    from xtddft_amd.qc import M, dints
+    mol = M(**MOLS["HF-631G"])
+    eri0, nuc0 = dints.eri_full_device(mol), dints.int1e_nuc_device(mol)
+    tab = dints.pair_table(mol)
+    d = tab.dev(0)
+    kinfo = torch.as_tensor(tab.ket_info_pairs(np.arange(tab.npair), tab.c0.astype(np.int32)), device="cuda")
+    cart = torch.zeros((tab.ncart_tot, tab.ncart_tot), dtype=torch.float64, device="cuda")
+    rc = hiplib.xt_int2e_cart(tab.npair, d["pinfo"].data_ptr(), d["pprim"].data_ptr(), d["eab"].data_ptr(), tab.npair,
+                              kinfo.data_ptr(), d["pprim"].data_ptr(), d["eab"].data_ptr(), tab.lmax, 2 * tab.lmax, 0.0,
+                              None, None, 0.0, 0, cart.data_ptr(), tab.ncart_tot,
+                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0
+    y = tab.rows_to_sph(tab.rows_to_sph(cart, 0).T.contiguous(), 0)
+    y = 0.5 * (y + y.T)
+    n = mol.nao
+    direct = y.index_select(0, d["sel"]).index_select(1, d["sel"]).reshape(n, n, n, n).cpu().numpy()
+    h = host("HF-631G")
+    dints.somf_g_device(mol, **h["p"], use_1c=False)
+    dints.int1e_pvp_device(mol)
+    eri1, nuc1 = dints.eri_full_device(mol), dints.int1e_nuc_device(mol)
+    assert np.array_equal(_bits(eri0), _bits(direct)) and np.array_equal(_bits(eri0), _bits(eri1))
+    assert np.array_equal(_bits(nuc0), _bits(nuc1))
+    assert np.abs(eri0 - mol.eri_full()).max() < 1e-12 and np.abs(nuc0 - mol.intor("int1e_nuc")).max() < 1e-11
+
+
+# --------------------------------------------------------------------------- end to end
+def test_triplet_molecule_end_to_end_with_generated_vso(torch, capsys):
+    """HF / 6-31G triplet ROKS with the sf-X2C core Hamiltonian; Vso from get_soDKH1_somf
+    (iop 'x2c', the primitive basis, one-centre SOMF) through vso_mo into SI_driver."""
+    import molecules
+    from xtddft_amd import (SF_TDA, SI_driver, XSF_TDA, XTDA, get_soDKH1_somf, states_from_sf_up, states_from_xsf,
+                            states_from_xtda, vso_mo)
+    from xtddft_amd.qc import ROKS
+    scf = ROKS(molecules.hf_mol(), "bhandhlyp").sfx2c1e()
+    scf.irrep_nelec = dict(molecules.HF_IRREP_NELEC)
+    scf.conv_tol = 1e-11
+    scf.kernel()
+    assert scf.converged
+    e_nr = molecules.hf_scf("ROKS").e_tot
+    print(f"sf-X2C - non-relativistic energy {scf.e_tot - e_nr:.6f} Ha")
+    assert -0.2 < scf.e_tot - e_nr < -0.01
+    vso_ao = get_soDKH1_somf(scf, scf.mol, iop="x2c", include_mf2e=True)
+    n = scf.mol.nao
+    assert vso_ao.shape == (3, n, n) and vso_ao.dtype == np.float64
+    assert np.abs(vso_ao + vso_ao.transpose(0, 2, 1)).max() < 1e-12 * np.abs(vso_ao).max()
+    mf = scf.to_meanfield()
+    vso = vso_mo(scf, vso_ao)
+    xsf = XSF_TDA(mf)
+    xsf.kernel(nstates=4)
+    xt = XTDA(mf.mol, mf, nstates=4)
+    xt.kernel()
+    up = SF_TDA(mf, isf=1)
+    up.kernel(nstates=3)
+    states = {'|S->': states_from_xsf(xsf), '|So>': states_from_xtda(xt), '|S+>': states_from_sf_up(up)}
+    nc, no, nv = xt.nc, xt.no, xt.nv
+    si = SI_driver(mf, 1.0, vso, ngs=1, states=states)
+    eso, v = si.kernel(printnum=5)
+    capsys.readouterr()
+    dim = 1 * 4 + 3 * (1 + 4) + 5 * 3
+    assert si.heff.shape == (dim, dim) and eso.shape == (dim,)
+    h, _, _ = si_ref.heff(vso, 1.0, nc, no, nv, states, 1)
+    RTOL = 1e-12                                                   # tests/test_gpu_si.py RTOL
+    print(f"max|dH| {np.abs(si.heff - h).max():.2e}, max|hso| {np.abs(si.hso).max():.3e} Ha, max|Vso_ao| {np.abs(vso_ao).max():.3e}")
+    assert np.abs(si.heff - h).max() < RTOL * np.abs(h).max()
+    assert np.abs(eso - np.linalg.eigvalsh(h)).max() < RTOL * np.linalg.norm(h, 2)
+    assert np.isrealobj(eso) and np.all(np.isfinite(eso))
+    assert abs(eso.sum() - np.trace(si.Omega).real) < 1e-11
+    assert 0.0 < np.abs(si.hso).max() < 1e-2
+    # zero-field splitting of the ground triplet: the levels whose largest component lies in |GS>
+    gs = [i for i in range(dim) if "GS" in si.v2state(v[:, i])[0]]
+    assert len(gs) == 3
+    lev = np.sort(eso[gs])
+    print(f"ZFS of the ground triplet: levels above its lowest {(lev - lev[0]) * 219474.63} cm^-1 (unpinned)")

@@ -19,7 +19,8 @@ from .utils import HA2EV, HA2EV_XSF, order_pyscf2my, so2st, st2so
 
 __all__ = ["Grid", "MeanField", "Mole", "HA2EV", "HA2EV_XSF", "order_pyscf2my", "so2st", "st2so",
            "XTDA", "SF_TDA", "SF_TDA_up", "SF_TDA_down", "XSF_TDA", "davidson1", "DeviceOperator", "OSsTDA",
-           "SI_driver", "si_couple", "states_from_xsf", "states_from_xtda", "states_from_sf_up"]
+           "SI_driver", "si_couple", "states_from_xsf", "states_from_xtda", "states_from_sf_up",
+           "get_soDKH1_somf", "vso_mo"]
 
 
 def __getattr__(name):   # lazy: importing the package must not require a GPU
@@ -41,6 +42,9 @@ def __getattr__(name):   # lazy: importing the package must not require a GPU
     if name in ("SI_driver", "si_couple", "states_from_xsf", "states_from_xtda", "states_from_sf_up"):
         from . import soc
         return getattr(soc, name)
+    if name in ("get_soDKH1_somf", "vso_mo"):
+        from . import somf
+        return getattr(somf, name)
     if name == "DeviceOperator":
         from .operator import DeviceOperator
         return DeviceOperator

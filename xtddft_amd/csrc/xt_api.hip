@@ -170,6 +170,21 @@ extern "C" int xt_int2e_cart(int npair, const int* pair_info, const double* pair
   return r ? fail(r, "int2e launch failed") : 0;
 }
 
+extern "C" int xt_hint_cart(int nbra, const int* bra_info, const double* bra_prim, const double* eb, int nket,
+                            const int* ket_info, const double* ket_prim, const double* ek, int lbra, int lket,
+                            int cross, long nrow_tot, double* out, long ldo, void* stream) {
+  if (nbra < 0 || nket < 0 || ldo < 0) return fail(XT_ERR_ARG, "xt_hint_cart: negative size");
+  if (lbra < 0 || lket < 0 || lbra > kHintMaxLBra || lbra + lket > kHintMaxL)
+    return fail(XT_ERR_ARG, "xt_hint_cart: bra order <= 8 and total order <= 14");
+  if (cross != 0 && cross != 1) return fail(XT_ERR_ARG, "xt_hint_cart: cross must be 0 or 1");
+  if (cross && nrow_tot <= 0) return fail(XT_ERR_ARG, "xt_hint_cart: cross needs nrow_tot > 0");
+  if ((long)nbra * nket > 0 && (!bra_info || !bra_prim || !eb || !ket_info || !ket_prim || !ek || !out))
+    return fail(XT_ERR_ARG, "xt_hint_cart: null table or output");
+  const int r = hint_cart(nbra, bra_info, bra_prim, eb, nket, ket_info, ket_prim, ek, lbra, lket, cross, nrow_tot,
+                          out, ldo, (hipStream_t)stream);
+  return r ? fail(r, "hint launch failed") : 0;
+}
+
 extern "C" int xt_eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info,
                           const double* shell_data, const double* sph, const double* ao_norm, int deriv,
                           double* out, long ldo, long comp_stride, void* stream) {

@@ -167,6 +167,12 @@ int int2e_cart(int npair, const int* pair_info, const double* pair_prim, const d
                const int* ket_info, const double* ket_prim, const double* ek, int lmax_orb, int lket,
                double omega, const double* q_bra, const double* q_ket, double q_thr, int diag, double* out,
                long ldo, hipStream_t st);
+// Coulomb integrals between Hermite-form distributions with stated orders (xt_hint.hip): bra
+// order <= kHintMaxLBra (two derivatives on an f f pair), total order <= kHintMaxL
+constexpr int kHintMaxLBra = 8, kHintMaxL = 14;
+int hint_cart(int nbra, const int* bra_info, const double* bra_prim, const double* eb, int nket,
+              const int* ket_info, const double* ket_prim, const double* ek, int lbra, int lket, int cross,
+              long nrow_tot, double* out, long ldo, hipStream_t st);
 int eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info, const double* dat,
             const double* sph, const double* norm, int deriv, double* out, long ldo, long comp_stride,
             hipStream_t st);

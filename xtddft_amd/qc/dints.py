@@ -26,6 +26,12 @@ compare them to 1e-12):
   exponent 1e24 with coefficient (s/pi)^1.5: the kernel's prefactor then tends to
   PySCF's 2 pi / p to 1e-20 relative);
 * ``eval_ao_device``   -- AO values (+ gradients) on grid points (PySCF ``eval_ao``).
+
+The spin-orbit mean field (``xtddft_amd.somf``) goes through a third kernel, ``xt_hint_cart``
+(``csrc/xt_hint.hip``: the same scheme with the Hermite order stated per table entry):
+
+* ``somf_g_device``    -- the two-electron spin-orbit mean field contracted semi-directly;
+* ``int1e_pvp_device`` -- <d mu|V_ne|d nu>: PySCF ``int1e_pnucp`` and the three cross products.
 """
 from __future__ import annotations
 
@@ -443,3 +449,269 @@ def eval_ao_device(mol, coords, deriv: int = 0, device: int = 0, out=None, block
                                      t_dat.data_ptr(), t_sph.data_ptr(), t_nrm.data_ptr(), int(bool(deriv)),
                                      out[0, g0:g1].data_ptr(), n, ng * n, st), "xt_eval_ao")
     return out if deriv else out[0]
+
+
+# ---------------------------------------------------------------- spin-orbit mean field
+class DerivPairTable:
+    """Ordered shell pairs (i, j) of a Mole with d/dr on the first function (``both``: on both,
+    the trace and the three cross products) as tables of ``xt_hint_cart``, usable as bra and as
+    ket.  ``use_1c``: only pairs whose two shells sit on one atom (the one-centre approximation
+    of the reference's SOMF term keeps the quartets whose four shells share an atom; ``atom``
+    gives each pair's).  Rows / columns of a pair are its Cartesian (a, b) block at ``c0``; the
+    spherical transform scatters straight to the dense AO pair index mu * nao + nu."""
+
+    def __init__(self, mol, use_1c: bool = False, both: bool = False):
+        from .ints import deriv_tables
+        sh = mol.shells
+        n = mol.nao
+        self.nao, self.both = n, both
+        self.ncomp = 4 if both else 3
+        ordered = [(i, j) for i in range(len(sh)) for j in range(len(sh))
+                   if not use_1c or sh[i].atom == sh[j].atom]
+        groups = {}
+        for k, (i, j) in enumerate(ordered):
+            groups.setdefault((sh[i].l, sh[j].l, sh[i].exps.size, sh[j].exps.size), []).append(k)
+        tabs = [None] * len(ordered)
+        for (la, lb, _, _), ks in groups.items():
+            sas, sbs = [sh[ordered[k][0]] for k in ks], [sh[ordered[k][1]] for k in ks]
+            a = np.stack([s.exps for s in sas])[:, :, None]
+            b = np.stack([s.exps for s in sbs])[:, None, :]
+            A = np.stack([s.center for s in sas])
+            B = np.stack([s.center for s in sbs])
+            cc = np.stack([s.coefs for s in sas])[:, :, None] * np.stack([s.coefs for s in sbs])[:, None, :]
+            AB = [(A - B)[:, d][:, None, None] for d in range(3)]
+            D = deriv_tables(la, lb, a, b, AB, cc, both)             # (comp, ca, cb, t, P, na, nb)
+            D = np.moveaxis(D, 4, 0).reshape(len(ks), -1, D.shape[3], a.shape[1] * b.shape[2])
+            p = (a + b).reshape(len(ks), -1)
+            P = ((a[..., None] * A[:, None, None, :] + b[..., None] * B[:, None, None, :])
+                 / (a + b)[..., None]).reshape(len(ks), -1, 3)
+            # primitive-pair screening as PairTable (the derivative's 2a is inside the table)
+            bound = np.abs(D).max(axis=(1, 2)) * (np.pi / p) ** 1.5 * np.maximum(1.0, np.sqrt(p))
+            for m, k in enumerate(ks):
+                keep = bound[m] >= PRIM_SCREEN
+                if not keep.any():
+                    keep[np.argmax(bound[m])] = True
+                tabs[k] = (np.ascontiguousarray(D[m][..., keep]), p[m][keep], P[m][keep])
+        extra = 2 if both else 1
+        order = sorted(range(len(ordered)), key=lambda k: (sh[ordered[k][0]].l + sh[ordered[k][1]].l,
+                                                           -tabs[k][1].size, k))
+        info, prim, eb, self.pairs, c0s = [], [], [], [], []
+        crow = q0 = e0 = 0
+        for k in order:
+            i, j = ordered[k]
+            D, p_k, P_k = tabs[k]
+            nab = sh[i].ncart * sh[j].ncart
+            info.append([sh[i].l + sh[j].l + extra, D.shape[0], p_k.size, q0, e0, crow, sh[i].atom if use_1c else 0, 0])
+            prim.append(np.column_stack([p_k, P_k]))
+            eb.append(D.ravel())
+            self.pairs.append((i, j))
+            c0s.append(crow)
+            crow += nab if not both else D.shape[0]
+            q0 += p_k.size
+            e0 += D.size
+        self.info = np.array(info, dtype=np.int32).reshape(-1, 8)
+        self.prim = np.concatenate(prim)
+        self.eb = np.concatenate(eb)
+        self.npair = len(self.pairs)
+        self.c0 = np.array(c0s, dtype=np.int64)
+        self.nab = np.array([sh[i].ncart * sh[j].ncart for i, j in self.pairs], dtype=np.int64)
+        self.atom = np.array([sh[i].atom for i, _ in self.pairs], dtype=np.int64)
+        self.ncart_tot = crow
+        self.order = int(self.info[:, 0].max())
+        self.mol = mol
+        self._dev = {}
+
+    def dev(self, device):
+        if device not in self._dev:
+            torch = _torch()
+            dv = torch.device(f"cuda:{device}")
+            self._dev[device] = dict(dev=dv, info=torch.as_tensor(self.info, device=dv),
+                                     prim=torch.as_tensor(self.prim, device=dv),
+                                     eb=torch.as_tensor(self.eb, device=dv))
+        return self._dev[device]
+
+    def ket_info(self, ks):
+        """Ket table of pairs ``ks`` with consecutive Cartesian column blocks: (info, ncol)."""
+        src = self.info[ks]
+        out = np.zeros_like(src)
+        nab = self.nab[ks]
+        out[:, 0] = src[:, 0]                  # order
+        out[:, 1:4] = src[:, 2:5]              # primitive pairs, first primitive, table offset
+        out[:, 4] = np.concatenate([[0], np.cumsum(nab)[:-1]])
+        out[:, 5] = 3 * nab
+        out[:, 6] = src[:, 6]                  # group tag (the atom of a one-centre table)
+        return out, int(nab.sum())
+
+    def sph_classes(self, ks, device, starts=None):
+        """Block transforms of the Cartesian blocks of pairs ``ks`` (at ``starts``, default their
+        table rows) to normalised spherical AO pairs: a list of (kron(T_li, T_lj) scaled per pair
+        by the AO norms, Cartesian index (npc, nc), spherical slot (npc, ns)) per (l_i, l_j) class,
+        and the (mu, nu) of every spherical slot in pair order."""
+        torch = _torch()
+        mol, sh = self.mol, self.mol.shells
+        dv = torch.device(f"cuda:{device}")
+        starts = self.c0[ks] if starts is None else starts
+        by = {}
+        mus, nus, s0 = [], [], 0
+        for pos, k in enumerate(ks):
+            i, j = self.pairs[k]
+            mu = mol.ao_loc[i] + np.arange(sh[i].nsph)[:, None]
+            nu = mol.ao_loc[j] + np.arange(sh[j].nsph)[None, :]
+            mu, nu = (x.ravel() for x in np.broadcast_arrays(mu, nu))
+            by.setdefault((sh[i].l, sh[j].l), []).append((starts[pos], s0, mol._norm[mu] * mol._norm[nu]))
+            mus.append(mu)
+            nus.append(nu)
+            s0 += mu.size
+        out = []
+        for (li, lj), items in by.items():
+            Tk = np.kron(_sph_transform(li), _sph_transform(lj))
+            ns, nc = Tk.shape
+            cidx = np.array([c for c, _, _ in items])[:, None] + np.arange(nc)[None, :]
+            sidx = np.array([s for _, s, _ in items])[:, None] + np.arange(ns)[None, :]
+            Tw = np.stack([w[:, None] * Tk for _, _, w in items])             # (npc, ns, nc)
+            out.append((torch.as_tensor(Tw, device=dv), torch.as_tensor(cidx, device=dv),
+                        torch.as_tensor(sidx, device=dv)))
+        return out, np.concatenate(mus), np.concatenate(nus)
+
+
+def deriv_pair_table(mol, use_1c: bool = False, both: bool = False) -> DerivPairTable:
+    cache = mol.__dict__.setdefault("_deriv_pair_tables", {})
+    key = (bool(use_1c), bool(both))
+    if key not in cache:
+        cache[key] = DerivPairTable(mol, use_1c, both)
+    return cache[key]
+
+
+def _blocks_to_sph(x, classes, nout):
+    """x (ncart, m) -> (nout, m): every class's blocks through its scaled transforms, rows
+    outside every block zero."""
+    torch = _torch()
+    y = torch.zeros((nout, x.shape[1]), dtype=torch.float64, device=x.device)
+    for Tw, cidx, sidx in classes:
+        y[sidx.reshape(-1)] = torch.bmm(Tw, x[cidx]).reshape(-1, x.shape[1])
+    return y
+
+
+def _hint(L, d, nbra, nket, kinfo, kprim, ek, lbra, lket, cross, nrow_tot, out, ldo, device):
+    _capi.check(L.xt_hint_cart(nbra, d["info"].data_ptr(), d["prim"].data_ptr(), d["eb"].data_ptr(), nket,
+                               kinfo.data_ptr(), kprim.data_ptr(), ek.data_ptr(), int(lbra), int(lket), int(cross),
+                               int(nrow_tot), out.data_ptr(), int(ldo), _stream(device)), "xt_hint_cart")
+
+
+def somf_chunk_pairs(tab: DerivPairTable, device: int, chunk_pairs=None) -> int:
+    """Ket pairs per launch of somf_g_device: the Cartesian block (3, ncart_tot, chunk columns),
+    its two transposes and the spherical block have to fit a quarter of the free HBM."""
+    if chunk_pairs is not None:
+        return max(1, min(int(chunk_pairs), tab.npair))
+    torch = _torch()
+    free = torch.cuda.mem_get_info(torch.device(f"cuda:{device}"))[0]
+    per_pair = 4 * 3 * 8 * max(tab.ncart_tot, tab.nao ** 2) * int(tab.nab.max())
+    return max(1, min(tab.npair, int(0.25 * free) // per_pair))
+
+
+def somf_g_device(mol, pLL, pLS, pSS, use_1c: bool = True, device: int = 0, chunk_pairs=None, timings=None):
+    """(gsoLL, gsoLS, gsoSS), each (3, nao, nao): the two-electron spin-orbit mean field of the
+    reference's get_fso2e (sfX2C_soDKH1.py:257-282) contracted semi-directly on the GPU.  With
+    K^l[mu nu, ka la] = eps_lmn (d_m mu  nu | d_n ka  la),
+        gLL[nu, la] = -2 K[mu nu, ka la] pSS[mu, ka]
+        gLS[mu, la] = -K[mu nu, ka la] pLS[nu, ka];   gLS[nu, la] -= K[mu nu, ka la] pLS[mu, ka]
+        gSS[mu, nu] = -2 K[mu nu, ka la] (pLL[la, ka] + pLL[ka, la]);   gSS[mu, ka] += 2 K[mu nu, ka la] pLL[nu, la]
+    K is evaluated in chunks of ket pairs (xt_hint_cart, cross mode) in a fixed order and
+    digested by matrix products; nothing is accumulated atomically, so two calls give the same
+    bits.  ``use_1c``: quartets with all four shells on one atom only (same-atom pairs, tagged by atom)."""
+    torch = _torch()
+    L = _capi.lib()
+    tab = deriv_pair_table(mol, use_1c)
+    d = tab.dev(device)
+    dv = d["dev"]
+    n = mol.nao
+    tm = {} if timings is None else timings
+
+    def timed(name, fn):
+        if timings is None:
+            return fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        tm.setdefault("_events", []).append((name, e0, e1))
+        return out
+
+    with torch.cuda.device(dv):
+        p_ll, p_ls, p_ss = (torch.as_tensor(np.array(x, dtype=np.float64), device=dv)
+                            for x in (pLL, pLS, pSS))
+        g_ll, g_ls, g_ss = (torch.zeros((3, n, n), dtype=torch.float64, device=dv) for _ in range(3))
+        # one-centre: the table holds same-atom pairs tagged with their atom, and the kernel skips
+        # quartets whose bra and ket tags differ -- every atom runs in the same launches
+        sel = np.arange(tab.npair)
+        row_cls, rmu, rnu = tab.sph_classes(sel, device)
+        rdense = torch.as_tensor(rmu * n + rnu, device=dv)
+        chunk = somf_chunk_pairs(tab, device, chunk_pairs)
+        for k0 in range(0, tab.npair, chunk):
+            ks = sel[k0:k0 + chunk]
+            kinfo_h, ncc = tab.ket_info(ks)
+            kinfo = torch.as_tensor(kinfo_h, device=dv)
+            cart = torch.zeros((3, tab.ncart_tot, ncc), dtype=torch.float64, device=dv)
+            timed("kernel", lambda: _hint(L, d, tab.npair, len(ks), kinfo, d["prim"], d["eb"], tab.order,
+                                          tab.order, 1, tab.ncart_tot, cart, ncc, device))
+
+            def transform():
+                col_cls, kap, lam = tab.sph_classes(ks, device, starts=kinfo_h[:, 4].astype(np.int64))
+                ncs = kap.size
+                x = cart.permute(1, 0, 2).reshape(tab.ncart_tot, 3 * ncc)
+                y = _blocks_to_sph(x, row_cls, rmu.size)                         # (rows, 3 ncc)
+                y = y.reshape(-1, 3, ncc).permute(2, 1, 0).reshape(ncc, -1)      # (ncc, 3 rows)
+                z = _blocks_to_sph(y, col_cls, ncs).reshape(ncs, 3, -1)          # (ncs, 3, rows)
+                kd = torch.zeros((3, n * n, ncs), dtype=torch.float64, device=dv)
+                kd[:, rdense] = z.permute(1, 2, 0)
+                return kd.reshape(3, n, n, ncs), kap, lam
+            K, kap, lam = timed("transform", transform)
+
+            def contract():
+                tk, tl = torch.as_tensor(kap, device=dv), torch.as_tensor(lam, device=dv)
+                one_k = torch.zeros((kap.size, n), dtype=torch.float64, device=dv)
+                one_l = torch.zeros((kap.size, n), dtype=torch.float64, device=dv)
+                one_k[torch.arange(kap.size, device=dv), tk] = 1.0
+                one_l[torch.arange(kap.size, device=dv), tl] = 1.0
+                g_ll.sub_(2.0 * torch.matmul(torch.einsum('xmnc,mc->xnc', K, p_ss[:, tk]), one_l))
+                g_ls.sub_(torch.matmul(torch.einsum('xmnc,nc->xmc', K, p_ls[:, tk]), one_l))
+                g_ls.sub_(torch.matmul(torch.einsum('xmnc,mc->xnc', K, p_ls[:, tk]), one_l))
+                g_ss.sub_(2.0 * torch.matmul(K, p_ll[tl, tk] + p_ll[tk, tl]))
+                g_ss.add_(2.0 * torch.matmul(torch.einsum('xmnc,nc->xmc', K, p_ll[:, tl]), one_k))
+            timed("contract", contract)
+            del cart, K
+        torch.cuda.synchronize(dv)
+        for name, e0, e1 in tm.pop("_events", []):
+            tm[name] = tm.get(name, 0.0) + e0.elapsed_time(e1) * 1e-3
+        return g_ll.cpu().numpy(), g_ls.cpu().numpy(), g_ss.cpu().numpy()
+
+
+def int1e_pvp_device(mol, device: int = 0):
+    """(4, nao, nao): W^sf = sum_m <d_m mu|V_ne|d_m nu> (PySCF int1e_pnucp) and the three
+    W^l = eps_lmn <d_m mu|V_ne|d_n nu> (the reference's get_wso) on the GPU: xt_hint_cart in
+    plain mode with the nuclei as kets of order 0 and exponent 1e24, as int1e_nuc_device."""
+    torch = _torch()
+    L = _capi.lib()
+    tab = deriv_pair_table(mol, False, both=True)
+    d = tab.dev(device)
+    dv = d["dev"]
+    natm, n = mol.natm, mol.nao
+    s = POINT_CHARGE_EXP
+    kinfo = np.zeros((natm, 8), dtype=np.int32)
+    kinfo[:, 1] = 1
+    kinfo[:, 2] = kinfo[:, 3] = kinfo[:, 4] = np.arange(natm)
+    kinfo[:, 5] = 1
+    kprim = np.column_stack([np.full(natm, s), mol.atom_coords()])
+    ek = -mol._charges * (s / np.pi) ** 1.5
+    with torch.cuda.device(dv):
+        cart = torch.zeros((tab.ncart_tot, natm), dtype=torch.float64, device=dv)
+        _hint(L, d, tab.npair, natm, torch.as_tensor(kinfo, device=dv), torch.as_tensor(kprim, device=dv),
+              torch.as_tensor(ek, device=dv), tab.order, 0, 0, 0, cart, natm, device)
+        v = cart.sum(1)
+        # rows of a pair are (c, a, b): one (a, b) block per component, 4 nab apart
+        out = torch.zeros((4, n * n), dtype=torch.float64, device=dv)
+        allp = np.arange(tab.npair)
+        for c in range(4):
+            cls, mu, nu = tab.sph_classes(allp, device, starts=tab.c0 + c * tab.nab)
+            out[c, torch.as_tensor(mu * n + nu, device=dv)] = _blocks_to_sph(v[:, None], cls, mu.size)[:, 0]
+        return out.reshape(4, n, n).cpu().numpy()

@@ -288,8 +288,10 @@ class Mole:
 
     def intor(self, name: str, comp=None, hermi=0, origin=(0.0, 0.0, 0.0), device=None):
         """PySCF names: int1e_ovlp, int1e_kin, int1e_nuc, int1e_r, int1e_ipovlp,
-        int1e_cg_irxp (comp 3; common gauge origin = ``origin``, PySCF's default 0), int2e.
-        ``device=k``: int1e_nuc and int2e through the GPU integral kernel (``qc.dints``)."""
+        int1e_cg_irxp (comp 3; common gauge origin = ``origin``, PySCF's default 0), int2e,
+        int1e_pnucp, and int1e_wso (comp 3, see ``_pvp``).
+        ``device=k``: int1e_nuc, int2e, int1e_pnucp and int1e_wso through the GPU integral
+        kernels (``qc.dints``)."""
         key = name.replace("_sph", "")
         if device is not None and key == "int1e_nuc":
             from .dints import int1e_nuc_device
@@ -310,7 +312,29 @@ class Mole:
             return self._intor_raw("irxp", origin)
         if key == "int2e":
             return self.eri_full()
+        if key in ("int1e_pnucp", "int1e_wso"):
+            w = self._pvp(device)
+            return w[0] if key == "int1e_pnucp" else w[1:]
         raise KeyError(name)
+
+    def _pvp(self, device=None):
+        """(4, nao, nao): sum_m <d_m mu|V_ne|d_m nu> (PySCF int1e_pnucp; symmetric) and
+        W^l = eps_lmn <d_m mu|V_ne|d_n nu> (int1e_wso, this package's name for the reference's
+        get_wso, sfX2C_soDKH1.py:202-216; antisymmetric), V_ne = -sum_A Z_A / |r - R_A|.  Every
+        ordered shell pair is evaluated on its own (``ints.DerivPair``)."""
+        if device is not None:
+            from .dints import int1e_pvp_device
+            return int1e_pvp_device(self, device)
+        from .ints import DerivPair
+        n = self._nao
+        out = np.zeros((4, n, n))
+        for i, si in enumerate(self.shells):
+            Ti = _sph_transform(si.l)
+            for j, sj in enumerate(self.shells):
+                blk = DerivPair(si, sj, both=True).nuclear(self._charges, self._coords)
+                out[:, self.ao_loc[i]:self.ao_loc[i + 1], self.ao_loc[j]:self.ao_loc[j + 1]] = \
+                    np.einsum('mi,dij,nj->dmn', Ti, blk, _sph_transform(sj.l))
+        return out * (self._norm[:, None] * self._norm[None, :])
 
     # -------------------------------------------------- density fitting
     def _aux_groups(self):
@@ -441,6 +465,42 @@ class Mole:
             T = _sph_transform(s.l)
             out[:, :, p0:p1] = np.einsum('xgc,mc->xgm', cart, T) * self._norm[p0:p1]
         return out if deriv else out[0]
+
+
+def get_xmol(mol):
+    """(xmol, contr_coeff): ``mol`` in its primitive basis and the (nao_x, nao) matrix of the
+    contracted normalised AOs in it (PySCF ``mf.with_x2c.get_xmol``).  Built from the basis
+    entries, one primitive shell per distinct exponent of an atom and angular momentum: ``Mole``
+    splits a general contraction into one Shell per coefficient column, and primitives that
+    several contractions share would otherwise appear twice and make the overlap singular."""
+    xbasis, slots = {}, {}
+    for el in dict.fromkeys(mol.elements):
+        ent, pos = [], {}
+        for sh in _basis.load(mol.basis, el):
+            for row in sh[1:]:
+                key = (int(sh[0]), float(row[0]))
+                if key not in pos:
+                    pos[key] = len(ent)
+                    ent.append([int(sh[0]), [float(row[0]), 1.0]])
+        xbasis[el], slots[el] = ent, pos
+    xmol = Mole(mol.atom, basis=xbasis, charge=mol.charge, spin=mol.spin, unit=mol.unit, symmetry=False)
+    first = {}
+    for k, s in enumerate(xmol.shells):
+        first.setdefault(s.atom, k)
+    c = np.zeros((xmol.nao, mol.nao))
+    col = 0
+    for ia, el in enumerate(mol.elements):
+        for sh in _basis.load(mol.basis, el):
+            l = int(sh[0])
+            prim = np.array(sh[1:], dtype=np.float64)
+            for ic in range(1, prim.shape[1]):
+                for e, coef in zip(prim[:, 0], prim[:, ic]):
+                    r0 = xmol.ao_loc[first[ia] + slots[el][(l, float(e))]]
+                    for m in range(2 * l + 1):
+                        # both AOs are N (coefficient) gto_norm r^l exp(-e r^2) S_lm
+                        c[r0 + m, col + m] += coef * mol._norm[col + m] / xmol._norm[r0 + m]
+                col += 2 * l + 1
+    return xmol, c
 
 
 def M(atom, basis="6-31G", charge=0, spin=0, unit="Angstrom", symmetry=False, verbose=0) -> Mole:

@@ -481,3 +481,127 @@ def eri2c(auxa: AuxShellSet, auxb: AuxShellSet, omega: float = 0.0) -> np.ndarra
     Y = np.einsum('atP,tcPk->aPck', auxa.Ek, X, optimize=True)                      # (nca, Pprim, ncb, kb)
     Y = np.einsum('aPck,Pj->jakc', Y, auxa.seg, optimize=True)
     return Y
+
+
+# ------------------------------------------------------------ derivative tables
+# The spin-orbit integrals of xtddft_amd/somf.py (the reference's sfX2C_soDKH1.py: int1e_pnucp,
+# get_wso, get_kint) carry d/dr_m on one or both functions of a pair.  A differentiated
+# Cartesian Gaussian is two Gaussians of neighbouring angular momentum,
+#     d_m g_l = 2 a g_{l + 1_m} - l_m g_{l - 1_m},
+# so the pair is again a Hermite expansion, one order higher per derivative; the exponent a
+# differs per primitive and sits inside the table.
+_EPS = ((0, 1, 2), (1, 2, 0), (2, 0, 1))          # (l, m, n) with eps_lmn = +1
+
+
+def _shifted(comp, m, d):
+    c = list(comp)
+    c[m] += d
+    return tuple(c)
+
+
+def deriv_tables(la: int, lb: int, a, b, AB, cc, both: bool = False):
+    """Hermite tables of a differentiated pair; a, b, cc are arrays of the primitive-pair
+    shape S (cc = the product of the contraction coefficients), AB[d] = A_d - B_d
+    broadcastable to S.
+
+    both=False: D[m, ca, cb, t] + S over hermite_index(la + lb + 1): (d_m a) b.
+    both=True:  D[c, ca, cb, t] + S over hermite_index(la + lb + 2): c = 0 the trace
+                sum_m (d_m a)(d_m b), c = 1 + l the cross products eps_lmn (d_m a)(d_n b).
+    """
+    a, b, cc = (np.asarray(x, dtype=np.float64) for x in (a, b, cc))
+    L = la + lb + (2 if both else 1)
+    E = [hermite_e(la + 1, lb + (1 if both else 0), a, b, AB[d]) for d in range(3)]
+    tuv = np.array(hermite_index(L)[0])
+    tt, uu, vv = tuv[:, 0], tuv[:, 1], tuv[:, 2]
+    S = np.broadcast(a, b, cc).shape
+    cA, cB = cart_comps(la), cart_comps(lb)
+
+    def prod(ca_, cb_):          # Hermite coefficients of the plain product g_ca g_cb
+        return E[0][ca_[0], cb_[0]][tt] * E[1][ca_[1], cb_[1]][uu] * E[2][ca_[2], cb_[2]][vv]
+
+    def d_first(ca_, cb_, m):    # (d_m g_ca) g_cb
+        v = 2.0 * a * prod(_shifted(ca_, m, 1), cb_)
+        if ca_[m] > 0:
+            v = v - ca_[m] * prod(_shifted(ca_, m, -1), cb_)
+        return v
+
+    def d_both(ca_, cb_, m, n):  # (d_m g_ca)(d_n g_cb)
+        up = _shifted(cb_, n, 1)
+        v = 2.0 * b * d_first(ca_, up, m)
+        if cb_[n] > 0:
+            v = v - cb_[n] * d_first(ca_, _shifted(cb_, n, -1), m)
+        return v
+
+    out = np.zeros((4 if both else 3, len(cA), len(cB), len(tuv)) + S)
+    for i, ca_ in enumerate(cA):
+        for j, cb_ in enumerate(cB):
+            if not both:
+                for m in range(3):
+                    out[m, i, j] = d_first(ca_, cb_, m) * cc
+                continue
+            d = [[d_both(ca_, cb_, m, n) for n in range(3)] for m in range(3)]
+            out[0, i, j] = (d[0][0] + d[1][1] + d[2][2]) * cc
+            for l, m, n in _EPS:
+                out[1 + l, i, j] = (d[m][n] - d[n][m]) * cc
+    return out
+
+
+class DerivPair:
+    """Ordered pair of contracted Cartesian shells with the first (``both``: both) function
+    differentiated, in the form ``eri_quartet`` and the device kernel take a shell pair:
+    Eab[row, 1, t, q] with rows (m, ca, cb) (``both``: (c, ca, cb), c as in deriv_tables),
+    order L = la + lb + 1 (+ 2).  (d a  b| is not (d b  a|: the pair is ordered."""
+
+    def __init__(self, sa, sb, both: bool = False):
+        self.sa, self.sb = sa, sb
+        a = sa.exps[:, None]
+        b = sb.exps[None, :]
+        AB = sa.center - sb.center
+        cc = sa.coefs[:, None] * sb.coefs[None, :]
+        D = deriv_tables(sa.l, sb.l, a, b, AB, cc, both)
+        self.ncomp = D.shape[0]
+        self.nab = D.shape[1] * D.shape[2]
+        self.L = sa.l + sb.l + (2 if both else 1)
+        self.Eab = D.reshape(self.ncomp * self.nab, 1, D.shape[3], -1)
+        p = a + b
+        self.p = p.ravel()
+        self.P = ((a[..., None] * sa.center + b[..., None] * sb.center) / p[..., None]).reshape(-1, 3)
+
+    def nuclear(self, charges, coords):
+        """sum_C -Z_C <rows| 1/|r - C| >: (ncomp, nca, ncb)."""
+        acc = np.zeros(self.Eab.shape[0])
+        for z, c in zip(charges, coords):
+            d = self.P - c
+            R = hermite_r(self.L, self.p, d[:, 0], d[:, 1], d[:, 2])
+            acc += -z * np.einsum('atq,tq->a', self.Eab[:, 0], R * (2.0 * np.pi / self.p))
+        return acc.reshape(self.ncomp, self.sa.ncart, self.sb.ncart)
+
+
+def cross3(x, ax_m: int, ax_n: int):
+    """eps_lmn x[.. m .. n ..] -> leading axis l (the axes m and n are removed)."""
+    x = np.moveaxis(x, (ax_m, ax_n), (0, 1))
+    return np.stack([x[m, n] - x[n, m] for _, m, n in _EPS])
+
+
+def eri_quartet_kets(bra, kets) -> np.ndarray:
+    """eri_quartet(bra, ket) for kets of one class (equal order, component rows and primitive
+    pair count) in one pass over the stacked ket primitives: (nket, nca, ncb, ncc, ncd)."""
+    K, nq = len(kets), kets[0].p.size
+    p = bra.p[:, None]
+    q = np.concatenate([k.p for k in kets])[None, :]
+    d = bra.P[:, None, :] - np.concatenate([k.P for k in kets])[None, :, :]
+    lk = kets[0].L
+    R = hermite_r(bra.L + lk, p * q / (p + q), d[..., 0], d[..., 1], d[..., 2])
+    pref = 2.0 * np.pi ** 2.5 / (p * q * np.sqrt(p + q))
+    idx, sign = _sum_table(bra.L, lk)
+    Rm = (R[idx] * pref).reshape(idx.shape + (bra.p.size, K, nq))     # (ntab, ntcd, P, K, q)
+    E = np.stack([k.Eab for k in kets])                               # (K, c, d, s, q)
+    X = np.einsum('tsPKq,s,Kcdsq->KtcdP', Rm, sign, E, optimize=True)
+    return np.einsum('abtP,KtcdP->Kabcd', bra.Eab, X, optimize=True)
+
+
+def somf_quartet(bra: DerivPair, ket: DerivPair) -> np.ndarray:
+    """K^l = eps_lmn (d_m a  b | d_n c  d) over Cartesian components: (3, nca, ncb, ncc, ncd)."""
+    g = eri_quartet(bra, ket)[:, 0, :, 0]                              # (3 nab, 3 ncd)
+    g = g.reshape(3, bra.sa.ncart, bra.sb.ncart, 3, ket.sa.ncart, ket.sb.ncart)
+    return cross3(g, 0, 3)

@@ -103,6 +103,16 @@ class _SCFBase:
         self._built = False
         return self
 
+    def sfx2c1e(self, c: float = None):
+        """Spin-free one-electron X2C core Hamiltonian (PySCF ``scf.sfx2c(mf)`` /
+        ``mf.sfx2c1e()``, test_SOCSI.py:141): ``get_hcore`` becomes
+        contr_coeff^T h1e(xmol) contr_coeff with h1e from ``somf.sfx2c1e`` in the primitive basis.
+        ``with_x2c.get_xmol(mol)`` is what ``somf.get_soDKH1_somf`` reads."""
+        from ..somf import X2C
+        self.with_x2c = X2C(self.mol) if c is None else X2C(self.mol, c)
+        self._built = False
+        return self
+
     def _use_cholesky(self):
         if self.with_df is not None:
             return False
@@ -124,6 +134,8 @@ class _SCFBase:
         t0 = time.perf_counter()
         self.s1e = mol.intor("int1e_ovlp")
         self.h1e = mol.intor("int1e_kin") + mol.intor("int1e_nuc", device=dev)
+        if getattr(self, "with_x2c", None) is not None:
+            self.h1e = self.with_x2c.get_hcore(dev)
         self.timings["int1e_s"] = time.perf_counter() - t0
         self.eri = self.eri_lr = None
         self._eri_k = self._eri_k_lr = None
