@@ -538,6 +538,35 @@ int xt_int2e_cart(int npair, const int* pair_info, const double* pair_prim, cons
 int xt_hint_cart(int nbra, const int* bra_info, const double* bra_prim, const double* eb,
                  int nket, const int* ket_info, const double* ket_prim, const double* ek,
                  int lbra, int lket, int cross, long nrow_tot, double* out, long ldo, void* hip_stream);
+/* First-derivative Coulomb integrals contracted with a two-particle density to a force on the
+   atoms: the two-electron part of an analytic nuclear gradient (the reference's
+   grad_jp/grad/usfcis.py get_jk / get_k terms; xtddft_amd/qc/grad.py builds the tables),
+     out[3A + m] += sum_{a on A} sum_{b,c,d} (d_m a  b|c d) Gamma_abcd,   m = x, y, z,
+     Gamma_abcd = sum_{t < nterm} wj[t] P_t[a,b] Q_t[c,d] + wk[t] P_t[a,c] Q_t[b,d],
+   d_m a being what the bra table holds for row (m, ca, cb): ints.py deriv_tables stores the
+   derivative with respect to the centre of a, 2 alpha g_{l+1_m} - l_m g_{l-1_m}, the negative of
+   the electron-coordinate derivative (the caller fixes the sign).  The integrals are
+   xt_hint_cart's and are consumed where they are formed; nothing of size pairs x pairs is written.
+     bra_info / bra_prim / eb   ordered pairs with the first function differentiated, as
+                                xt_hint_cart's bra: order la + lb + 1, rows (m, ca, cb), nrow = 3 nab
+     bra_ao[4k+0..3]            first Cartesian AO of a, of b, ncart(b), atom of a
+     ket_info / ket_prim / ek   plain shell pairs c >= d, as xt_hint_cart's ket (ncol = ncd)
+     ket_ao[4j+0..3]            first Cartesian AO of c, of d, ncart(d), 1 when c != d (the thread
+                                then adds the (d, c) image of Gamma)
+     wj, wk                     nterm host doubles each, 1 <= nterm <= 8
+     p, q                       device, nterm matrices nao x nao each over Cartesian components,
+                                row-major, not necessarily symmetric
+   A thread owns one bra entry and at most `strip` ket entries (every nstrip-th one, nstrip =
+   ceil(nket / strip)); the strips and then the bra
+   entries of an atom are summed in table order by two small kernels, without atomics: equal
+   inputs give equal bits.  `work` (device) holds at least 3 nbra (ceil(nket / strip) + 1) doubles,
+   nwork states its length.  `out` (device, 3 natm) is accumulated into.  lbra / lket bound the
+   orders as in xt_hint_cart (lbra <= 8, lbra + lket <= 14); an entry above them adds nothing. */
+int xt_grad_jk(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao,
+               int nket, const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao,
+               int lbra, int lket, int nterm, const double* wj, const double* wk, const double* p,
+               const double* q, long nao, int strip, int natm, double* work, long nwork, double* out,
+               void* hip_stream);
 /* AO values (deriv 0) or values and gradients (deriv 1) of normalised spherical
    AOs on grid points (PySCF mol.eval_ao / ni.block_loop, SF_TDA.py:63-68, the AO
    input of cache_xc_kernel / nr_uks_fxc, XTDA.py:504,514), device pointers:

@@ -10,6 +10,8 @@ Reference-compatible entry points (PySCF-style operator API):
 * ``OSsTDA(mol, mf, ...)``              (xtddft/sTDA/os_sTDA.py)
 * ``SI_driver(mf, S, Vso, ...)``        (x2c_hamiltonian/driver/si_driver.py) and the
   ``states_from_xsf`` / ``states_from_xtda`` / ``states_from_sf_up`` helpers
+* ``SF_TDA_down(mf).nuc_grad_method()`` / ``SF_TDA_up(mf).nuc_grad_method()`` and
+  ``qc.UHF(mol).nuc_grad_method()``     (xtddft/grad_jp/grad/usfcis.py; ``xtddft_amd/grad.py``)
 
 The arithmetic runs in the HIP library ``_lib/libxtddft_amd.so`` (C ABI in
 ``include/xtddft_amd.h``); there is no CPU fallback.

@@ -185,6 +185,27 @@ extern "C" int xt_hint_cart(int nbra, const int* bra_info, const double* bra_pri
   return r ? fail(r, "hint launch failed") : 0;
 }
 
+extern "C" int xt_grad_jk(int nbra, const int* bra_info, const double* bra_prim, const double* eb,
+                          const int* bra_ao, int nket, const int* ket_info, const double* ket_prim,
+                          const double* ek, const int* ket_ao, int lbra, int lket, int nterm, const double* wj,
+                          const double* wk, const double* p, const double* q, long nao, int strip, int natm,
+                          double* work, long nwork, double* out, void* stream) {
+  if (nbra < 0 || nket < 0 || nao < 0 || natm < 0 || nwork < 0) return fail(XT_ERR_ARG, "xt_grad_jk: negative size");
+  if (strip < 1) return fail(XT_ERR_ARG, "xt_grad_jk: strip must be at least 1");
+  if (lbra < 0 || lket < 0 || lbra > kHintMaxLBra || lbra + lket > kHintMaxL)
+    return fail(XT_ERR_ARG, "xt_grad_jk: bra order <= 8 and total order <= 14");
+  if (nterm < 1 || nterm > kGradMaxTerms) return fail(XT_ERR_ARG, "xt_grad_jk: nterm must be 1..8");
+  if (!wj || !wk) return fail(XT_ERR_ARG, "xt_grad_jk: null weights");
+  if (nbra == 0 || nket == 0 || natm == 0) return 0;   // nothing to add
+  if (!bra_info || !bra_prim || !eb || !bra_ao || !ket_info || !ket_prim || !ek || !ket_ao || !p || !q || !work ||
+      !out)
+    return fail(XT_ERR_ARG, "xt_grad_jk: null table, density, workspace or output");
+  if (nwork < grad_jk_work(nbra, nket, strip)) return fail(XT_ERR_ARG, "xt_grad_jk: workspace too small");
+  const int r = grad_jk(nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra, lket, nterm,
+                        wj, wk, p, q, nao, strip, natm, work, out, (hipStream_t)stream);
+  return r ? fail(r, "grad_jk launch failed") : 0;
+}
+
 extern "C" int xt_eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info,
                           const double* shell_data, const double* sph, const double* ao_norm, int deriv,
                           double* out, long ldo, long comp_stride, void* stream) {

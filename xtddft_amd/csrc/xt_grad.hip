@@ -1,0 +1,208 @@
+// First-derivative Coulomb integrals contracted with a two-particle density straight to a force
+// on the atoms -- the two-electron part of every analytic nuclear gradient (xtddft_amd/qc/grad.py,
+// xtddft_amd/grad.py; the reference's grad_jp/grad/usfcis.py, there PySCF's get_jk / get_k over
+// libcint's int2e_ip1):
+//
+//   g[A][m] = sum_{a in A} sum_{b,c,d} (d_m a  b | c d) Gamma_abcd,      m = x, y, z
+//   Gamma_abcd = sum_{t < nterm} wj[t] P_t[a,b] Q_t[c,d] + wk[t] P_t[a,c] Q_t[b,d]
+//
+// d_m a is what the bra table holds (qc/ints.py deriv_tables: the derivative with respect to the
+// centre of a, the negative of the electron-coordinate derivative; the host fixes the sign);
+// P_t, Q_t are arbitrary (not necessarily symmetric) matrices over Cartesian components.  The integrals are k_hint_cart's
+// (xt_hint.hip): the bra is an ordered DerivPair entry (rows (m, ca, cb), order la + lb + 1), the
+// ket a plain shell pair c >= d of the pair table; where k_hint_cart stores pref * acc, this
+// kernel multiplies it by its Gamma element and adds it to one of three sums, so no integral
+// reaches HBM.  For c != d the thread adds the (d, c) image of Gamma itself: (ab|cd) = (ab|dc).
+//
+//   bra_info / bra_prim / eb, ket_info / ket_prim / ek: as xt_hint_cart (row0 / col0 unused)
+//   bra_ao[4 k + .]: first Cartesian AO of a, of b, ncart(b), atom of a
+//   ket_ao[4 j + .]: first Cartesian AO of c, of d, ncart(d), 1 when c != d (add the image)
+//
+// Reduction without atomics: a thread owns one bra entry and a strip of at most `strip` ket entries
+// (strip s takes the entries s, s + nstrip, ...: the table is sorted by primitive count, and consecutive
+// entries would put all the long quartets into the first strips) and writes partial[strip][bra][3];
+// k_grad_strips sums the strips of a bra entry in
+// strip order, k_grad_atoms folds the bra entries into their atoms in table order.  Two calls on
+// the same inputs give the same bits.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include "xt_internal.h"
+#include "xt_hermite.h"
+#include "xt_hint_dev.h"
+
+namespace xt {
+
+struct GradTerms {
+  int nterm;
+  double wj[kGradMaxTerms], wk[kGradMaxTerms];
+};
+
+// Gamma of one (bra block, ket block) is kept per thread when it has at most this many elements
+// (every s / p quartet: 9 x 9); larger blocks recompute the element per primitive quartet
+constexpr int kGradCache = 81;
+
+__device__ __forceinline__ double grad_gamma(const GradTerms& tm, const double* __restrict__ P,
+                                             const double* __restrict__ Q, long n, long ia, long ib, long ic,
+                                             long id) {
+  double g = 0.0;
+  const long n2 = n * n;
+  for (int t = 0; t < tm.nterm; ++t) {
+    const double* p = P + t * n2;
+    const double* q = Q + t * n2;
+    g += tm.wj[t] * p[ia * n + ib] * q[ic * n + id] + tm.wk[t] * p[ia * n + ic] * q[ib * n + id];
+  }
+  return g;
+}
+
+// MAXL: largest total order, MAXLB: largest bra order (they size R / S and M)
+template <int MAXL, int MAXLB>
+__global__ void __launch_bounds__(64)
+k_grad_jk(int nbra, const int* __restrict__ bra_info, const double* __restrict__ bra_prim,
+          const double* __restrict__ eb, const int* __restrict__ bra_ao, int nket,
+          const int* __restrict__ ket_info, const double* __restrict__ ket_prim, const double* __restrict__ ek,
+          const int* __restrict__ ket_ao, GradTerms tm, const double* __restrict__ P,
+          const double* __restrict__ Q, long nao, int nstrip, double* __restrict__ partial) {
+  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (long)nbra * nstrip) return;
+  const int s = (int)(id / nbra), k = (int)(id % nbra);
+  const int* bi = bra_info + 8 * k;
+  const int lb = bi[0], nrow = bi[1], npp = bi[2], bq0 = bi[3], be0 = bi[4];
+  const int a0 = bra_ao[4 * k], b0 = bra_ao[4 * k + 1], ncb = bra_ao[4 * k + 2] > 0 ? bra_ao[4 * k + 2] : 1;
+  const int nab = nrow / 3, ntb = ntuv(lb);
+  double g[3] = {0.0, 0.0, 0.0};
+  double R[ntuv(MAXL)], S[ntuv(MAXL)], M[ntuv(MAXLB)], G[kGradCache];
+  for (int j = s; j < nket; j += nstrip) {   // at most `strip` entries
+    const int* ki = ket_info + 8 * j;
+    const int lk = ki[0], nr = ki[1], kr0 = ki[2], ke0 = ki[3], ncol = ki[5];
+    const int c0 = ket_ao[4 * j], d0 = ket_ao[4 * j + 1], image = ket_ao[4 * j + 3];
+    const int ncd = ket_ao[4 * j + 2] > 0 ? ket_ao[4 * j + 2] : 1;
+    const int L = lb + lk, ntk = ntuv(lk);
+    if (L > MAXL || lb > MAXLB) continue;   // an entry above the declared bounds adds nothing
+    const bool cached = nab * ncol <= kGradCache;
+    if (cached)
+      for (int c = 0; c < ncol; ++c) {
+        const long ic = c0 + c / ncd, idd = d0 + c % ncd;
+        for (int ab = 0; ab < nab; ++ab) {
+          const long ia = a0 + ab / ncb, ib = b0 + ab % ncb;
+          double v = grad_gamma(tm, P, Q, nao, ia, ib, ic, idd);
+          if (image) v += grad_gamma(tm, P, Q, nao, ia, ib, idd, ic);
+          G[c * nab + ab] = v;
+        }
+      }
+    for (int q = 0; q < npp; ++q) {
+      const double* pp = bra_prim + 4 * (long)(bq0 + q);
+      const double p = pp[0];
+      for (int r = 0; r < nr; ++r) {
+        const double* cp = ket_prim + 4 * (long)(kr0 + r);
+        const double sx = cp[0];
+        hint_r<MAXL>(L, p * sx / (p + sx), pp[1] - cp[1], pp[2] - cp[2], pp[3] - cp[3], R, S);
+        const double pref = 2.0 * pow(M_PI, 2.5) / (p * sx * sqrt(p + sx));
+        for (int c = 0; c < ncol; ++c) {
+          // M[t] = sum_u (-1)^{|u|} E^c_u(r) R[t + u]
+          const double* e = ek + ke0 + ((long)c * ntk) * nr + r;
+          for (int it = 0; it < ntb; ++it) M[it] = 0.0;
+          int iu = 0;
+          for (int nu = 0; nu <= lk; ++nu)
+            for (int tu = nu; tu >= 0; --tu)
+              for (int uu = nu - tu; uu >= 0; --uu, ++iu) {
+                const int vu = nu - tu - uu;
+                const double w = ((nu & 1) ? -1.0 : 1.0) * e[(long)iu * nr];
+                if (w == 0.0) continue;
+                int it = 0;
+                for (int nt = 0; nt <= lb; ++nt)
+                  for (int tt = nt; tt >= 0; --tt)
+                    for (int ut = nt - tt; ut >= 0; --ut, ++it)
+                      M[it] += w * R[tuv_pos(tt + tu, ut + uu, nt - tt - ut + vu)];
+              }
+          const long ic = c0 + c / ncd, idd = d0 + c % ncd;
+          for (int ab = 0; ab < nab; ++ab) {
+            double gam;
+            if (cached) {
+              gam = G[c * nab + ab];
+            } else {
+              const long ia = a0 + ab / ncb, ib = b0 + ab % ncb;
+              gam = grad_gamma(tm, P, Q, nao, ia, ib, ic, idd);
+              if (image) gam += grad_gamma(tm, P, Q, nao, ia, ib, idd, ic);
+            }
+            gam *= pref;
+            for (int m = 0; m < 3; ++m) {
+              const double* ea = eb + be0 + ((long)(m * nab + ab) * ntb) * npp + q;
+              double acc = 0.0;
+              for (int it = 0; it < ntb; ++it) acc += ea[(long)it * npp] * M[it];
+              g[m] += gam * acc;
+            }
+          }
+        }
+      }
+    }
+  }
+  double* out = partial + 3 * ((long)s * nbra + k);
+  out[0] = g[0]; out[1] = g[1]; out[2] = g[2];
+}
+
+// bsum[k][m] = sum_s partial[s][k][m], s ascending
+__global__ void k_grad_strips(int nbra, int nstrip, const double* __restrict__ partial, double* __restrict__ bsum) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = 3 * (long)nbra;
+  if (i >= n) return;
+  double v = 0.0;
+  for (int s = 0; s < nstrip; ++s) v += partial[s * n + i];
+  bsum[i] = v;
+}
+
+// out[A][m] += sum_{k: atom(k) = A} bsum[k][m], k ascending; one thread per (A, m)
+__global__ void k_grad_atoms(int nbra, int natm, const int* __restrict__ bra_ao, const double* __restrict__ bsum,
+                             double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 3 * natm) return;
+  const int A = i / 3, m = i % 3;
+  double v = 0.0;
+  for (int k = 0; k < nbra; ++k)
+    if (bra_ao[4 * k + 3] == A) v += bsum[3 * (long)k + m];
+  out[i] += v;
+}
+
+long grad_jk_work(int nbra, int nket, int strip) {
+  const long nstrip = ((long)nket + strip - 1) / strip;
+  return 3 * (long)nbra * (nstrip + 1);
+}
+
+int grad_jk(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao, int nket,
+            const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao, int lbra, int lket,
+            int nterm, const double* wj, const double* wk, const double* P, const double* Q, long nao, int strip,
+            int natm, double* work, double* out, hipStream_t st) {
+  if (nbra == 0 || nket == 0 || natm == 0) return 0;
+  if (hint_boys_ensure(st)) return XT_ERR_HIP;
+  GradTerms tm;
+  tm.nterm = nterm;
+  for (int t = 0; t < kGradMaxTerms; ++t) {
+    tm.wj[t] = t < nterm ? wj[t] : 0.0;
+    tm.wk[t] = t < nterm ? wk[t] : 0.0;
+  }
+  const int nstrip = (int)(((long)nket + strip - 1) / strip);   // <= nket
+  const long n = (long)nbra * nstrip;
+  double* partial = work;
+  double* bsum = work + 3 * n;
+  const int blk = 64;
+  const dim3 grid((unsigned)((n + blk - 1) / blk));
+#define XT_GRAD(ML, MB)                                                                                  \
+  hipLaunchKernelGGL((k_grad_jk<ML, MB>), grid, dim3(blk), 0, st, nbra, bra_info, bra_prim, eb, bra_ao, \
+                     nket, ket_info, ket_prim, ek, ket_ao, tm, P, Q, nao, nstrip, partial)
+  if (lbra <= 4 && lbra + lket <= 6)   // s, p shells: (d p p | p p) 3 + 2
+    XT_GRAD(6, 4);
+  else if (lbra <= 6 && lbra + lket <= 10)   // d shells: (d d d | d d) 5 + 4
+    XT_GRAD(10, 6);
+  else if (lbra <= kHintMaxLBra && lbra + lket <= kHintMaxL)   // f shells: (d f f | f f) 7 + 6
+    XT_GRAD(kHintMaxL, kHintMaxLBra);
+  else
+    return XT_ERR_ARG;
+#undef XT_GRAD
+  if (hipGetLastError() != hipSuccess) return XT_ERR_HIP;
+  hipLaunchKernelGGL(k_grad_strips, dim3((unsigned)((3 * (long)nbra + 63) / 64)), dim3(64), 0, st, nbra, nstrip,
+                     partial, bsum);
+  hipLaunchKernelGGL(k_grad_atoms, dim3((unsigned)((3 * natm + 63) / 64)), dim3(64), 0, st, nbra, natm, bra_ao,
+                     bsum, out);
+  return hipGetLastError() == hipSuccess ? 0 : XT_ERR_HIP;
+}
+
+}  // namespace xt

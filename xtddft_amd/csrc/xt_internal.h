@@ -173,6 +173,15 @@ constexpr int kHintMaxLBra = 8, kHintMaxL = 14;
 int hint_cart(int nbra, const int* bra_info, const double* bra_prim, const double* eb, int nket,
               const int* ket_info, const double* ket_prim, const double* ek, int lbra, int lket, int cross,
               long nrow_tot, double* out, long ldo, hipStream_t st);
+// first-derivative Coulomb integrals contracted with a two-particle density to forces on the
+// atoms (xt_grad.hip): the orders of hint_cart, up to kGradMaxTerms (P_t, Q_t) density pairs;
+// work holds grad_jk_work() doubles
+constexpr int kGradMaxTerms = 8;
+long grad_jk_work(int nbra, int nket, int strip);
+int grad_jk(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao, int nket,
+            const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao, int lbra, int lket,
+            int nterm, const double* wj, const double* wk, const double* P, const double* Q, long nao, int strip,
+            int natm, double* work, double* out, hipStream_t st);
 int eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info, const double* dat,
             const double* sph, const double* norm, int deriv, double* out, long ldo, long comp_stride,
             hipStream_t st);

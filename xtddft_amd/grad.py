@@ -1,0 +1,204 @@
+"""Analytic nuclear gradients of spin-flip TDA (CIS) states on a UHF reference: the reference's
+USF-CIS gradient (``xtddft/grad_jp/grad/usfcis.py``) with its API,
+
+    g = SF_TDA_down(mf).nuc_grad_method()      # or SF_TDA_up(mf)
+    g.state = 2                                # 1-based, as the reference
+    de = g.kernel()                            # (natm, 3) Ha / Bohr
+
+``grad_elec`` follows usfcis.py:16-256 in content: the relaxed-density pieces T_alpha, T_beta and
+the symmetric / antisymmetric parts of the transition density (85-95), the Lagrangian right-hand
+side Q / w (104-126), the Z-vector (127-150, ``qc.grad.solve_zvector``: J / K on the device), the
+energy-weighted density W (``im0``, 158-183) and the final contraction (193-253).  Its
+``td_grad.get_jk`` / ``get_k`` derivative-integral terms -- ground state, T + Z and X_S / X_A --
+are the terms of **one** ``xt_grad_jk`` call (``qc.grad.grad_jk_device``); with D = D0 + (T + Z^S)
+the cross terms of ground state and T + Z are D x D - (T + Z^S) x (T + Z^S), which keeps the
+call at the kernel's eight density pairs.
+
+Spin-flip-up is the same derivation with alpha and beta exchanged (J / K of a Hartree-Fock
+reference do not tell the spins apart): the driver hands the spin-reversed orbitals to the
+same function.
+
+Hartree-Fock only: a functional (kernel-derivative terms), density fitting (as the reference,
+usfcis.py:284), an ROHF reference and method != 0 raise NotImplementedError.
+"""
+from __future__ import annotations
+
+import time
+
+import numpy as np
+
+from .qc import grad as _g
+
+
+def _scf_of(td):
+    mf = td.mf
+    if getattr(mf, "is_rohf", False):
+        raise NotImplementedError("spin-flip gradients need a UHF reference (the reference's "
+                                  "usfcis-rohf.py is not a working code path)")
+    ref = mf.extra.get("qc_scf") if hasattr(mf, "extra") else None
+    scf = ref() if ref is not None else None          # a weak reference: the mean field does not own the SCF
+    if scf is None:
+        if str(getattr(mf, "xctype", "HF")) != "HF":
+            raise NotImplementedError(f"spin-flip gradients for xc = {mf.xc!r}: Hartree-Fock only")
+        raise ValueError("the gradient needs the SCF object the mean field came from (qc UHF.to_meanfield()), "
+                         "still alive")
+    _g.check_gradient_mf(scf)
+    return scf
+
+
+def sf_amplitude(td, state_idx):
+    """x (nvir_f, nocc_i) of root ``state_idx`` (0-based), normalised: flipped-to virtuals by
+    flipped-from occupieds (usfcis.py:61-73 for spin-flip-down; spin-flip-up is stored (o, v))."""
+    v = np.asarray(td.v)[:, state_idx]
+    nc, no, nv = td.nc, td.no, td.nv
+    if td.isf == -1:
+        d1, d2, d3 = nc * nv, nc * nv + nc * no, nc * nv + nc * no + no * nv
+        x = np.zeros((nc + no, no + nv))
+        x[:nc, :no] = v[d1:d2].reshape(nc, no)
+        x[:nc, no:] = v[:d1].reshape(nc, nv)
+        x[nc:, :no] = v[d3:].reshape(no, no)
+        x[nc:, no:] = v[d2:d3].reshape(no, nv)
+    else:
+        x = v.reshape(nc, nv)
+    return x.T / np.linalg.norm(x)
+
+
+def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None):
+    """Electronic part of the gradient of E_UHF + omega, (natm, 3).  ``x_ab`` (nvir_b, nocc_a) in
+    the labels of spin-flip-down; ``flip``: the state is spin-flip-up, and "a" below is beta."""
+    tm = {} if timings is None else timings
+    mol = scf.mol
+    s = (1, 0) if flip else (0, 1)
+    mo_coeff = [scf.mo_coeff[s[0]], scf.mo_coeff[s[1]]]
+    mo_occ = [scf.mo_occ[s[0]], scf.mo_occ[s[1]]]
+    fock_ao = scf.get_hcore()[None] + np.asarray(scf._veff)
+    orboa, orbva = mo_coeff[0][:, mo_occ[0] > 0], mo_coeff[0][:, mo_occ[0] == 0]
+    orbob, orbvb = mo_coeff[1][:, mo_occ[1] > 0], mo_coeff[1][:, mo_occ[1] == 0]
+    nocca, noccb = orboa.shape[1], orbob.shape[1]
+    fockamo = mo_coeff[0].T @ fock_ao[s[0]] @ mo_coeff[0]
+    fockbmo = mo_coeff[1].T @ fock_ao[s[1]] @ mo_coeff[1]
+    if x_ab.shape != (orbvb.shape[1], nocca):
+        raise ValueError(f"amplitude shape {x_ab.shape}, expected {(orbvb.shape[1], nocca)}")
+
+    def get_jk(dms):             # J / K do not depend on which spin a density belongs to
+        return scf.get_jk(dm=np.asarray(dms), hermi=0)
+
+    # T_alpha (occupied-occupied), T_beta (virtual-virtual), X in the AO basis
+    ta = -x_ab.T @ x_ab
+    tb = x_ab @ x_ab.T
+    dmta = orboa @ ta @ orboa.T
+    dmtb = orbvb @ tb @ orbvb.T
+    dmxab = orbvb @ x_ab @ orboa.T
+    dmSx, dmAx = (dmxab + dmxab.T) / 2, (dmxab - dmxab.T) / 2
+    vj, vk = get_jk((dmta, dmtb, dmSx, dmAx))
+    vkmo = mo_coeff[1].T @ (vk[2] + vk[3]) @ mo_coeff[0]          # K[X_S] + K[X_A]: beta rows, alpha columns
+    veff0dooa = vj[0] + vj[1] - vk[0]
+    veff0doob = vj[0] + vj[1] - vk[1]
+    # right-hand side of the Z-vector equations
+    wvoa = 2.0 * (orbva.T @ veff0dooa @ orboa + fockamo[nocca:, :nocca] @ ta.T - vkmo[noccb:, nocca:].T @ x_ab)
+    wvob = 2.0 * (orbvb.T @ veff0doob @ orbob - tb @ fockbmo[:noccb, noccb:].T + x_ab @ vkmo[:noccb, :nocca].T)
+    t0 = time.perf_counter()
+    za, zb, res, ncyc = _g.solve_zvector(_SpinView(scf, s), wvoa, wvob, cphf_conv_tol, cphf_max_cycle)
+    tm["zvector_s"] = time.perf_counter() - t0
+    tm["zvector_cycles"], tm["zvector_residual"] = ncyc, float(res)
+    z1ao = np.asarray([orbva @ za @ orboa.T, orbvb @ zb @ orbob.T])
+    zs = (z1ao + z1ao.transpose(0, 2, 1)) * 0.5
+    vjz, vkz = get_jk(zs)
+    veff = (vjz[0] + vjz[1])[None] - vkz
+    # energy-weighted density W
+    im0a = np.zeros_like(fockamo)
+    im0b = np.zeros_like(fockbmo)
+    im0a[:nocca, :nocca] = (fockamo[:nocca, :nocca] + orboa.T @ (veff0dooa + veff[0]) @ orboa
+                            + ta @ fockamo[:nocca, :nocca] - x_ab.T @ vkmo[noccb:, :nocca])
+    im0b[:noccb, :noccb] = fockbmo[:noccb, :noccb] + orbob.T @ (veff0doob + veff[1]) @ orbob
+    im0b[noccb:, noccb:] = tb @ fockbmo[noccb:, noccb:].T - x_ab @ vkmo[noccb:, :nocca].T
+    im0a[nocca:, :nocca] = za @ fockamo[:nocca, :nocca].T
+    im0b[noccb:, :noccb] = zb @ fockbmo[:noccb, :noccb].T - 2.0 * x_ab @ vkmo[:noccb, :nocca].T
+    im0 = mo_coeff[0] @ im0a @ mo_coeff[0].T + mo_coeff[1] @ im0b @ mo_coeff[1].T
+    # relaxed difference densities T + Z^S and the ground state
+    dmz1dooa, dmz1doob = zs[0] + dmta, zs[1] + dmtb
+    oo0a, oo0b = orboa @ orboa.T, orbob @ orbob.T
+    t0 = time.perf_counter()
+    de = _g.contract_1e(mol, _g.hcore_generator(mol), _g.get_ovlp(mol), oo0a + oo0b + dmz1dooa + dmz1doob, im0)
+    tm["one_electron_s"] = time.perf_counter() - t0
+    # two-electron part: ground state + (T + Z^S) cross terms as D x D - TZ x TZ, and X_S, X_A
+    da, db = oo0a + dmz1dooa, oo0b + dmz1doob
+    tz = dmz1dooa + dmz1doob
+    terms = [_g.jk_terms(1, 0, da + db, da + db), _g.jk_terms(-1, 0, tz, tz),
+             _g.jk_terms(0, -1, da, da), _g.jk_terms(0, 1, dmz1dooa, dmz1dooa),
+             _g.jk_terms(0, -1, db, db), _g.jk_terms(0, 1, dmz1doob, dmz1doob),
+             _g.jk_terms(0, -2, dmSx, dmSx),
+             (0.0, 2.0, dmAx - dmAx.T, dmAx)]       # -2 vk[X_A] . (X_A[p,q] - X_A[q,p])
+    t0 = time.perf_counter()
+    st = {}
+    de += _g.grad_jk_device(mol, terms, device, stats=st)
+    tm["grad_jk_s"] = time.perf_counter() - t0
+    tm["buckets"] = st.get("buckets", [])
+    return de
+
+
+class _SpinView:
+    """The SCF object with its spin labels in the order ``s`` (what solve_zvector reads)."""
+
+    def __init__(self, scf, s):
+        self._scf = scf
+        self.mo_coeff = [scf.mo_coeff[s[0]], scf.mo_coeff[s[1]]]
+        self.mo_occ = [scf.mo_occ[s[0]], scf.mo_occ[s[1]]]
+        self.mo_energy = [scf.mo_energy[s[0]], scf.mo_energy[s[1]]]
+        self._veff = [scf._veff[s[0]], scf._veff[s[1]]]
+
+    def get_hcore(self):
+        return self._scf.get_hcore()
+
+    def get_jk(self, dm=None, hermi=1):
+        return self._scf.get_jk(dm=dm, hermi=hermi)
+
+
+class SFGradients:
+    """``SF_TDA_down(mf).nuc_grad_method()`` / ``SF_TDA_up(mf).nuc_grad_method()`` with the
+    reference's attributes (usfcis.py:261-331): ``state`` (1-based), ``cphf_conv_tol``,
+    ``cphf_max_cycle`` (the values its solver actually runs with, usfcis.py:145-148), ``atmlst``."""
+
+    cphf_max_cycle = 500
+    cphf_conv_tol = 1e-10
+
+    def __init__(self, td):
+        if td.method != 0:
+            raise NotImplementedError("spin-flip gradients are built for method = 0 only")
+        self.base = td
+        self._scf = _scf_of(td)
+        self.mol = self._scf.mol
+        self.state = 1
+        self.atmlst = None
+        self.de = None
+        self.timings = {}
+
+    def grad_nuc(self, mol=None, atmlst=None):
+        return _g.grad_nuc(mol or self.mol, atmlst)
+
+    def grad_elec(self, atmlst=None):
+        td = self.base
+        if getattr(td, "v", None) is None:
+            raise RuntimeError("run the SF-TDA kernel() first")
+        if not 1 <= self.state <= np.asarray(td.v).shape[1]:
+            raise ValueError(f"state {self.state} is not among the computed roots")
+        conv = getattr(td, "converged", None)
+        if td.davidson and conv is not None and not bool(np.asarray(conv)[self.state - 1]):
+            raise RuntimeError(f"root {self.state} of the Davidson solve is not converged")
+        dev = getattr(self._scf, "_device", None)
+        if dev is None:
+            raise RuntimeError("the gradient runs on the GPU (xt_grad_jk, device J / K): call "
+                               "mf.to_device() before the SCF")
+        de = grad_elec(self._scf, sf_amplitude(td, self.state - 1), td.isf == 1, dev, self.cphf_conv_tol,
+                       self.cphf_max_cycle, self.timings)
+        return de if atmlst is None else de[list(atmlst)]
+
+    def kernel(self, state=None, atmlst=None):
+        if state is not None:
+            self.state = state
+        if atmlst is None:
+            atmlst = self.atmlst
+        else:
+            self.atmlst = atmlst
+        self.de = self.grad_elec(atmlst) + self.grad_nuc(atmlst=atmlst)
+        return self.de

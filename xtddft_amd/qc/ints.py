@@ -577,6 +577,30 @@ class DerivPair:
         return acc.reshape(self.ncomp, self.sa.ncart, self.sb.ncart)
 
 
+def kinetic_deriv1(sa, sb) -> np.ndarray:
+    """<d_m a| -1/2 nabla^2 |b> over Cartesian components, (3, nca, ncb), d_m on the electron
+    coordinate: d_m g_l = l_m g_{l - 1_m} - 2 a g_{l + 1_m} (the negative of the centre derivative that
+    ``deriv_tables`` holds) with the primitive's 2 a folded into the coefficients of a shell one
+    unit higher (``ShellPair.kinetic`` on the two shifted shells)."""
+    import dataclasses
+    la = sa.l
+    up = ShellPair(dataclasses.replace(sa, l=la + 1, coefs=2.0 * sa.exps * sa.coefs), sb, kin=True,
+                   hermite=False).kinetic()
+    pos_up = {c: i for i, c in enumerate(cart_comps(la + 1))}
+    out = np.empty((3, len(cart_comps(la)), up.shape[1]))
+    for i, ca in enumerate(cart_comps(la)):
+        for m in range(3):
+            out[m, i] = -up[pos_up[_shifted(ca, m, 1)]]
+    if la > 0:
+        dn = ShellPair(dataclasses.replace(sa, l=la - 1), sb, kin=True, hermite=False).kinetic()
+        pos_dn = {c: i for i, c in enumerate(cart_comps(la - 1))}
+        for i, ca in enumerate(cart_comps(la)):
+            for m in range(3):
+                if ca[m] > 0:
+                    out[m, i] += ca[m] * dn[pos_dn[_shifted(ca, m, -1)]]
+    return out
+
+
 def cross3(x, ax_m: int, ax_n: int):
     """eps_lmn x[.. m .. n ..] -> leading axis l (the axes m and n are removed)."""
     x = np.moveaxis(x, (ax_m, ax_n), (0, 1))

@@ -24,6 +24,7 @@ Convergence: Pulay DIIS on (effective) Fock matrices, stop when |dE| <
 from __future__ import annotations
 
 import dataclasses
+import weakref
 
 import numpy as np
 import scipy.linalg
@@ -60,6 +61,7 @@ class _SCFBase:
         self.grids = None
         self.verbose = 0
         self.converged = False
+        self.last_energy_change = None   # |E_n - E_{n-1}| of the converged SCF cycle
         self.e_tot = 0.0
         self.scf_summary = {}
         self.mo_coeff = self.mo_occ = self.mo_energy = None
@@ -112,6 +114,13 @@ class _SCFBase:
         self.with_x2c = X2C(self.mol) if c is None else X2C(self.mol, c)
         self._built = False
         return self
+
+    def nuc_grad_method(self):
+        """Analytic nuclear gradient of the converged mean field (PySCF ``mf.nuc_grad_method()``):
+        UHF only (``qc.grad.Gradients``); ROHF / ROKS, a functional and density fitting raise
+        NotImplementedError."""
+        from .grad import Gradients
+        return Gradients(self)
 
     def _use_cholesky(self):
         if self.with_df is not None:
@@ -540,6 +549,7 @@ class UHF(_SCFBase):
                 print(f"cycle {cycle} E= {e_tot:.12f} |g|= {gnorm:.2e}")
             if e_last is not None and abs(e_tot - e_last) < self.conv_tol and gnorm < tol_grad:
                 self.converged = True
+                self.last_energy_change = abs(e_tot - e_last)
                 dms = dms_new
                 break
             e_last = e_tot
@@ -700,7 +710,7 @@ def _meanfield(mf, chol_tol):
         out.nlc, out.nlc_pars, out.nlc_rho_min = True, mf.nlc, mf.nlc_rho_min
         out.nlc_grids = Grid(ao=mf.ao_nlc, weights=np.ascontiguousarray(g.weights),
                              coords=np.ascontiguousarray(g.coords))
-    out.extra.update(dict(s1e=mf.s1e, orbsym=getattr(mf, "orbsym", None), qc_mol=mol))
+    out.extra.update(dict(s1e=mf.s1e, orbsym=getattr(mf, "orbsym", None), qc_mol=mol, qc_scf=weakref.ref(mf)))
     if not mf.restricted_open:
         out.extra["spin_square"] = mf.spin_square()
     return out

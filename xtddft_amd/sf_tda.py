@@ -122,12 +122,14 @@ def deal_v_davidson(mf, v):
 
 
 def davidson_process(mf, nstates, method, isf=-1, device=0, shard=(0, 1), return_operator=False,
-                     collinear_samples=DAVIDSON_SAMPLES):
+                     collinear_samples=DAVIDSON_SAMPLES, tol=1e-7, tol_residual=None, lindep=1e-14):
+    """``tol`` / ``lindep`` default to the reference's (SF_TDA.py:382-406); ``tol_residual`` (default
+    sqrt(tol)) bounds the residual norm of a converged root -- what a gradient's accuracy follows."""
     vind, hdiag = gen_tda_operation_sf(mf, isf, method, device=device, shard=shard,
                                        collinear_samples=collinear_samples)
     x0 = init_guess(mf, nstates, isf)
-    conv, e, x1, icyc = _dav.davidson1(vind, x0, hdiag, tol=1e-7, lindep=1e-14, nroots=nstates,
-                                       max_cycle=3000, device=device,
+    conv, e, x1, icyc = _dav.davidson1(vind, x0, hdiag, tol=tol, lindep=lindep, nroots=nstates,
+                                       max_cycle=3000, tol_residual=tol_residual, device=device,
                                        lockstep=shard[1] > 1)
     v = np.array(x1).T
     if isf == -1:   # SF_TDA.py:400-401
@@ -151,8 +153,11 @@ def _dense(op):
 class _SFBase:
     isf = 0
 
-    def __init__(self, mf, method=0, davidson=True, device=0, shard=(0, 1), collinear_samples=None):
+    def __init__(self, mf, method=0, davidson=True, device=0, shard=(0, 1), collinear_samples=None,
+                 conv_tol=1e-7, tol_residual=None, lindep=1e-14):
+        """``conv_tol`` / ``tol_residual`` / ``lindep``: the Davidson thresholds (``davidson_process``)."""
         _check_method(method)
+        self.conv_tol, self.tol_residual, self.lindep = conv_tol, tol_residual, lindep
         self.mf = mf
         self.method = method
         self.collinear_samples = collinear_samples
@@ -180,11 +185,18 @@ class _SFBase:
         if self.davidson:
             self.e, self.v, self.converged, self._op = davidson_process(
                 self.mf, nstates, self.method, self.isf, self.device, self.shard, return_operator=True,
-                collinear_samples=self.collinear_samples or DAVIDSON_SAMPLES)
+                collinear_samples=self.collinear_samples or DAVIDSON_SAMPLES, tol=self.conv_tol,
+                tol_residual=self.tol_residual, lindep=self.lindep)
         else:
             self.A = self.get_Amat()
             self.e, self.v = scipy.linalg.eigh(self.A)
         return self.e[:nstates] * HA2EV, self.v[:, :nstates]
+
+    def nuc_grad_method(self):
+        """Analytic nuclear gradient of a root (``xtddft_amd.grad.SFGradients``; the reference's
+        USFTDA.nuc_grad_method, grad_jp/grad/usfcis.py:368): UHF / Hartree-Fock, method 0."""
+        from .grad import SFGradients
+        return SFGradients(self)
 
     # ------------------------------------------------ state-to-state moments
     def transition_dipoles(self, op_ao=None):
