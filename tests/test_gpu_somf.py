@@ -4,7 +4,7 @@ semi-direct spin-orbit mean-field contraction built on it (``qc.dints.somf_g_dev
 
 Kernel bound, elementwise, as tests/test_gpu_int_paths.py holds xt_int2e_cart to:
 |dev - ref| <= kappa(L) 2^-53 sabs, with ref and sabs (the same sum over the absolute values of
-every factor) from the 40-digit machinery of tests/int_ref.py (``ref_hint`` below generalises
+every factor) from the 40-digit machinery of tests/int_ref.py (``ref_hint`` of tests/hint_ref.py generalises
 ``ref_int2e`` to stated orders, row counts and the cross mode) and kappa(L) the stored figure of
 tests/golden/int_ref.npz (8 x the host's error at total order L, floor 64).  The fixture stops
 at L = 13; L = 14, reached only by (d f  f|d f  f), takes the largest stored kappa: the figure
@@ -23,8 +23,8 @@ import numpy as np
 import pytest
 
 import int_cases as ic
-import int_ref
 import si_ref
+from hint_ref import as_ket, ref_hint, shell, tables
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +32,6 @@ SENTINEL = -7777.25
 GUARD = 64
 U = 2.0 ** -53
 
-CENTRES = np.array([[0.0, 0.0, 0.0], [0.9, -0.4, 0.3], [-0.5, 0.7, 1.1], [0.2, 1.3, -0.8]])
 # (la, lb, lc, ld), primitives per shell, centre of each shell
 CASES = [
     ((0, 0, 0, 0), (3, 1, 1, 3), (0, 1, 2, 3)),
@@ -65,92 +64,6 @@ def kappa():
 
 def _bits(a):
     return np.ascontiguousarray(a).view(np.int64)
-
-
-def shell(l, nprim, centre, seed):
-    from xtddft_amd.qc.gto import Shell, gto_norm
-    rng = np.random.default_rng(seed)
-    exps = 0.4 * 3.1 ** np.arange(nprim) * (1.0 + 0.3 * rng.random(nprim))
-    coefs = (0.5 + rng.random(nprim)) * gto_norm(l, exps)
-    return Shell(int(centre), l, CENTRES[centre].copy(), exps, coefs)
-
-
-def tables(pairs, unit):
-    """xt_hint_cart tables of DerivPair entries; a pair's output offset advances by unit * nab
-    (unit 3: plain mode, its rows are (m, a, b); unit 1: cross mode)."""
-    from xtddft_amd.qc.ints import DerivPair
-    info, prim, e = [], [], []
-    q0 = e0 = o0 = 0
-    for sa, sb in pairs:
-        dp = DerivPair(sa, sb)
-        tab = dp.Eab[:, 0]
-        info.append([dp.L, tab.shape[0], dp.p.size, q0, e0, o0, 0, 0])
-        prim.append(np.column_stack([dp.p, dp.P]))
-        e.append(tab.ravel())
-        q0 += dp.p.size
-        e0 += tab.size
-        o0 += unit * dp.nab
-    return np.array(info, dtype=np.int32), np.concatenate(prim), np.concatenate(e), o0
-
-
-def as_ket(info):
-    """bra rows (order, nrow, npp, prim0, e0, row0) -> ket rows (order, nprim, prim0, e0, col0, ncol)."""
-    out = np.zeros_like(info)
-    out[:, 0], out[:, 1:4], out[:, 4], out[:, 5] = info[:, 0], info[:, 2:5], info[:, 5], info[:, 1]
-    return out
-
-
-def ref_hint(binfo, bprim, eb, kinfo, kprim, ek, cross, nrow_tot, ldo):
-    """int_ref.ref_int2e for xt_hint_cart: orders and row counts read from the tables, and in
-    cross mode the eps_lmn combination of the (m | n) blocks.  (ref, sabs, L) of shape
-    (ncomp, nrow_tot, ldo), ncomp = 3 (cross) or 1."""
-    import mpmath as mp
-    LD, WIDE = int_ref.LD, int_ref.WIDE
-    ncomp = 3 if cross else 1
-    zero = LD(0) if WIDE else mp.mpf(0)
-    ref = np.full((ncomp, nrow_tot, ldo), zero, dtype=LD if WIDE else object)
-    sab = ref.copy()
-    Lmap = np.full((ncomp, nrow_tot, ldo), -1, dtype=np.int64)
-    bprim, kprim = np.asarray(bprim).reshape(-1, 4), np.asarray(kprim).reshape(-1, 4)
-    with mp.workdps(int_ref.DPS):
-        for j in range(len(kinfo)):
-            for k in range(len(binfo)):
-                lb, nrow, npp, bq0, be0, row0 = (int(x) for x in binfo[k][:6])
-                lk, nr, kr0, ke0, col0, ncol = (int(x) for x in kinfo[j][:6])
-                L, nt, nu = lb + lk, int_ref.ntuv(lb), int_ref.ntuv(lk)
-                E = int_ref._wide_array(np.asarray(eb[be0:be0 + nrow * nt * npp]).reshape(nrow, nt, npp))
-                K = int_ref._wide_array(np.asarray(ek[ke0:ke0 + ncol * nu * nr]).reshape(ncol, nu, nr))
-                idx, sign = int_ref._sum_index(lb, lk)
-                Ks = K * (sign[None, :, None].astype(LD) if WIDE else sign[None, :, None].astype(int).astype(object))
-                blk = np.full((nrow, ncol), zero, dtype=ref.dtype)
-                blka = blk.copy()
-                for q in range(npp):
-                    p = mp.mpf(float(bprim[bq0 + q, 0]))
-                    P = [mp.mpf(float(x)) for x in bprim[bq0 + q, 1:]]
-                    for r in range(nr):
-                        s = mp.mpf(float(kprim[kr0 + r, 0]))
-                        C = [mp.mpf(float(x)) for x in kprim[kr0 + r, 1:]]
-                        Rt = int_ref.hermite_r_mp(L, p * s / (p + s), P[0] - C[0], P[1] - C[1], P[2] - C[2])
-                        pref = int_ref._wide(2 * mp.pi ** 2.5 / (p * s * mp.sqrt(p + s)))
-                        Rg = np.array([int_ref._wide(x) for x in Rt], dtype=ref.dtype)[idx]
-                        blk += pref * (E[:, :, q] @ (Rg @ Ks[:, :, r].T))
-                        blka += abs(pref) * (np.abs(E[:, :, q]) @ (np.abs(Rg) @ np.abs(K[:, :, r]).T))
-                if not cross:
-                    ref[0, row0:row0 + nrow, col0:col0 + ncol] = blk
-                    sab[0, row0:row0 + nrow, col0:col0 + ncol] = blka
-                    Lmap[0, row0:row0 + nrow, col0:col0 + ncol] = L
-                    continue
-                nab, ncd = nrow // 3, ncol // 3
-                b4 = blk.reshape(3, nab, 3, ncd)
-                a4 = blka.reshape(3, nab, 3, ncd)
-                for l, m, n in ((0, 1, 2), (1, 2, 0), (2, 0, 1)):
-                    ref[l, row0:row0 + nab, col0:col0 + ncd] = b4[m, :, n] - b4[n, :, m]
-                    sab[l, row0:row0 + nab, col0:col0 + ncd] = a4[m, :, n] + a4[n, :, m]
-                    Lmap[l, row0:row0 + nab, col0:col0 + ncd] = L
-
-    def f64(a):
-        return a.astype(np.float64) if WIDE else np.array([float(x) for x in a.ravel()]).reshape(a.shape)
-    return f64(ref), f64(sab), Lmap
 
 
 def launch(torch, hiplib, bra, ket, cross, nrow_tot, ldo):

@@ -195,6 +195,12 @@ def default_strip(nbra, nket):
     return int(max(1, min(64, nbra * nket // 65536)))
 
 
+def work_size(nbra, nket, strip):
+    """Doubles of workspace one ``xt_grad_jk`` launch needs (``grad_jk_work`` of csrc/xt_grad.hip):
+    the partial sums of every strip and the per-entry sums."""
+    return 3 * nbra * ((nket + strip - 1) // strip + 1)
+
+
 def grad_jk_device(mol, terms, device: int = 0, strip=None, stats=None):
     """(natm, 3): sum over ``terms`` = [(wj, wk, P, Q)] (P, Q (nao, nao) over the spherical AOs,
     arbitrary) of the derivative-ERI contraction in the module docstring, through ``xt_grad_jk``.
@@ -222,7 +228,7 @@ def grad_jk_device(mol, terms, device: int = 0, strip=None, stats=None):
             for k0, k1, lk in tab.ket_ranges:
                 nb, nk = b1 - b0, k1 - k0
                 sl = default_strip(nb, nk) if strip is None else int(strip)
-                nwork = 3 * nb * ((nk + sl - 1) // sl + 1)
+                nwork = work_size(nb, nk, sl)
                 work = torch.empty(nwork, dtype=torch.float64, device=dv)
                 if stats is not None:
                     torch.cuda.synchronize(dv)
