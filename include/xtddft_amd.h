@@ -580,6 +580,40 @@ int xt_grad_jk(int nbra, const int* bra_info, const double* bra_prim, const doub
 int xt_eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info,
                const double* shell_data, const double* sph, const double* ao_norm, int deriv,
                double* out, long ldo, long comp_stride, void* hip_stream);
+/* The exchange-correlation force on the atoms at fixed spin density matrices: the nuclear
+   derivative of the XC potential matrix contracted with the ground-state density (PySCF
+   grad.uks.get_vxc, the vxc1[:, 1:] the reference's grad_hb/tduks_sfu.py:168-177 adds to the
+   mean-field gradient; xtddft_amd/qc/grad.py grad_xc_device), without grid-weight derivatives:
+     out[3A + x] += sum_{s < nspin} sum_{g < ngrid} sum_{mu on A}
+                      d_x phi_mu(g) e_s(g, mu) + (sum_{k = x,y,z} h_s(k, g) d_x d_k phi_mu(g)) c_s(g, mu)
+   (the caller applies the factor -2).  The AO first and second derivatives are evaluated where
+   they are consumed; no derivative plane is written.  Device pointers:
+     coords, shell_info, shell_data, sph, ao_norm   as xt_eval_ao (l <= 4)
+     shell_atom[s]      the atom (row of out) of shell s; shells of one atom need not be adjacent
+     lmax               bound of l over the shell table, 0 <= lmax <= 4; a shell above it, or one
+                        whose AO range leaves [0, nao), adds nothing
+     xctype             XT_XC_LDA: the first term only -- h and c are not read and may be null;
+                        XT_XC_GGA: both terms
+     h[(4 s + k) ldg + g]       k = 1..3: w_g d eps / d(d_k rho_s), the "eff" layout of the XC
+                                derivatives without any halving; plane k = 0 (d eps / d rho_s) is
+                                part of e and is never read
+     e[(s nao + mu) ldg + g]    e_s = b_s D_s with b_s = h_s(0) phi + sum_k h_s(k) d_k phi
+     c[(s nao + mu) ldg + g]    c_s = phi D_s
+   e and c are AO-major ([ao][g], ldg >= ngrid doubles between AOs) so that the lanes of a wave,
+   which are 64 consecutive grid points of one shell, read consecutive doubles; the GEMM engine
+   gives that layout as D_s b_s^T.  Reduction without atomics: a block (one shell x a tile of 64
+   grid points in GGA mode, where its four waves share out the four weights of the bracket, of
+   256 points in LDA mode) writes one partial sum; the grid tiles of a shell and then the shells
+   of an atom are summed in ascending order by two small kernels, so equal inputs give equal
+   bits.  `work` (device) holds at least 3 nshell (ceil(ngrid / 64) + 1) doubles in either mode,
+   nwork states its length.  `out` (device, 3 natm) is accumulated into.  XT_ERR_ARG before any
+   launch: negative sizes, ldg < ngrid, lmax outside 0..4, nspin not 1 or 2, xctype not LDA /
+   GGA, nwork too small, more than 2^31 blocks, a null pointer that would be read. */
+int xt_grad_xc(int ngrid, const double* coords, int nshell, const int* shell_info,
+               const double* shell_data, const double* sph, const double* ao_norm,
+               const int* shell_atom, int lmax, int natm, int nao, int nspin, int xctype,
+               const double* h, const double* e, const double* c, long ldg, double* work, long nwork,
+               double* out, void* hip_stream);
 
 #ifdef __cplusplus
 }

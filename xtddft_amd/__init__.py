@@ -12,6 +12,9 @@ Reference-compatible entry points (PySCF-style operator API):
   ``states_from_xsf`` / ``states_from_xtda`` / ``states_from_sf_up`` helpers
 * ``SF_TDA_down(mf).nuc_grad_method()`` / ``SF_TDA_up(mf).nuc_grad_method()`` and
   ``qc.UHF(mol).nuc_grad_method()``     (xtddft/grad_jp/grad/usfcis.py; ``xtddft_amd/grad.py``)
+* ``qc.UKS(mol, xc).to_device().nuc_grad_method()``: the UKS ground-state gradient, LDA / GGA,
+  pure and global hybrid (the mean-field gradient xtddft/grad_hb/tduks_sfu.py starts from;
+  ``xtddft_amd/qc/grad.py`` ``KSGradients``)
 
 The arithmetic runs in the HIP library ``_lib/libxtddft_amd.so`` (C ABI in
 ``include/xtddft_amd.h``); there is no CPU fallback.

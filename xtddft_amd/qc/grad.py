@@ -17,7 +17,18 @@
 * ``solve_zvector`` -- the UCPHF Z-vector equations (usfcis.py:127-150) by a host-driven
   preconditioned GMRES whose response J / K come from ``DeviceEngine.get_jk``;
 * ``Gradients`` -- ``UHF.nuc_grad_method()``: the T = Z = X = 0 subset of the excited-state
-  formula with W the energy-weighted density.
+  formula with W the energy-weighted density;
+* ``grad_xc_device`` -- the nuclear derivative of the XC potential matrix contracted with the
+  ground-state density (PySCF ``grad.uks.get_vxc``; the ``vxc1[:, 1:]`` of the reference's
+  ``grad_hb/tduks_sfu.py:168-177``) on a grid held fixed in space, through the engine's GEMMs and
+  the library kernel ``xt_grad_xc`` (``csrc/xt_grad_xc.hip``),
+
+      g[A, x] = -2 sum_s sum_g sum_{mu on A} d_x phi_mu e_s[g, mu] + (sum_k h_s[k, g] d_x d_k phi_mu) c_s[g, mu]
+
+  with h_s = w vxc_s in the "eff" layout (d eps / d rho_s, d eps / d(d_k rho_s); nothing halved),
+  b_s = h_s[0] phi + sum_k h_s[k] d_k phi, e_s = b_s D_s and c_s = phi D_s;
+* ``KSGradients`` -- ``UKS.nuc_grad_method()`` after ``to_device()``: LDA / GGA functionals, pure
+  and global hybrid, without grid-weight derivatives (``grid_response = False``).
 """
 from __future__ import annotations
 
@@ -27,11 +38,14 @@ import time
 import numpy as np
 
 from .. import _capi
+from . import xc as _xc
 from .gto import _sph_transform
 from .ints import DerivPair, hermite_r, kinetic_deriv1
 
 MAX_TERMS = 8
 MAX_CHOL_TOL = 1e-10     # loosest ERI Cholesky tolerance a gradient accepts (check_gradient_mf)
+XC_TILE = 64             # grid points per block of xt_grad_xc in GGA mode (csrc/xt_grad_xc.hip)
+XC_CHUNK_BYTES = 1 << 28  # e and c of one grid chunk of grad_xc_device stay below this
 # bra / ket order bounds of the kernel's three dispatch buckets (s p | d | f shells)
 BRA_BOUNDS = (4, 6, 8)
 KET_BOUNDS = (2, 4, 6)
@@ -426,3 +440,188 @@ class Gradients:
             self.atmlst = atmlst
         self.de = self.grad_elec(atmlst) + self.grad_nuc(atmlst=atmlst)
         return self.de
+
+
+# ------------------------------------------------------------------ UKS ground state
+def xc_work_size(ngrid, nshell):
+    """Doubles of workspace one ``xt_grad_xc`` call needs (``grad_xc_work`` of csrc/xt_grad_xc.hip)."""
+    return 3 * nshell * ((ngrid + XC_TILE - 1) // XC_TILE + 1)
+
+
+def default_xc_chunk(nao, ngrid):
+    """Grid points per ``xt_grad_xc`` call: the largest multiple of 256 at which e and c of both
+    spins (4 nao doubles per point) stay below ``XC_CHUNK_BYTES``, at least 256, at most the grid."""
+    return int(min(max(ngrid, 1), max(256, XC_CHUNK_BYTES // (32 * max(nao, 1)) // 256 * 256)))
+
+
+def grad_xc_device(mf, d0a, d0b, chunk=None, stats=None):
+    """(natm, 3): the XC part of the UKS gradient at the spin densities d0a, d0b on the mean
+    field's grid, points and weights held fixed (module docstring).  rho and vxc come from the
+    device engine; per chunk of ``chunk`` grid points (``default_xc_chunk``) the products
+    e_s = D_s b_s^T and c_s = D_s phi^T run on the engine's FP64 MFMA GEMM in the AO-major layout
+    the kernel reads, then one ``xt_grad_xc`` call adds the chunk's force.  ``stats``: a dict that
+    receives the seconds of the GEMMs and of the kernel and the bytes of h, e and c it read."""
+    import torch
+    from .dints import _sph_table, ao_shell_tables
+    eng = getattr(mf, "device_engine", None)
+    if eng is None or mf.xctype not in ("LDA", "GGA"):
+        raise RuntimeError("grad_xc_device needs a built LDA / GGA mean field on a device (mf.to_device())")
+    mol = mf.mol
+    gga = mf.xctype == "GGA"
+    L = _capi.lib()
+    dv = eng.dev
+    n, natm, nshell = mol.nao, mol.natm, len(mol.shells)
+    ng = int(eng.w.shape[0])
+    chunk = default_xc_chunk(n, ng) if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    info, dat = ao_shell_tables(mol)
+    with torch.cuda.device(dv):
+        def t(x):
+            return torch.as_tensor(np.ascontiguousarray(x), device=dv)
+        dms = t(np.asarray([d0a, d0b], dtype=np.float64))
+        rho = torch.stack([eng._rho(dms[0]), eng._rho(dms[1])])
+        vxc = _xc.eval_xc_eff_torch(mf.xc, rho, deriv=1)[1]
+        h = vxc * eng.w                                                          # (2, ncomp, G)
+        coords = t(np.asarray(mf.grids.coords, dtype=np.float64))
+        t_info, t_dat, t_sph, t_nrm = t(info), t(dat), t(_sph_table()), t(mol._norm)
+        t_atom = t(np.array([s.atom for s in mol.shells], dtype=np.int32))
+        lmax = max(s.l for s in mol.shells)
+        out = torch.zeros((natm, 3), dtype=torch.float64, device=dv)
+        nwork = xc_work_size(min(chunk, ng), nshell)
+        work = torch.empty(nwork, dtype=torch.float64, device=dv)
+        st = ctypes.c_void_p(torch.cuda.current_stream(dv).cuda_stream)
+        ao = eng.ao
+        tg = tk = 0.0
+        nbytes = 0
+        for g0 in range(0, ng, chunk):
+            g1 = min(ng, g0 + chunk)
+            m = g1 - g0
+            if stats is not None:
+                torch.cuda.synchronize(dv)
+                t0 = time.perf_counter()
+            hc = torch.zeros((2, 4, m), dtype=torch.float64, device=dv)
+            hc[:, :h.shape[1]] = h[:, :, g0:g1]
+            a0 = ao[0, g0:g1]
+            e = torch.empty((2, n, m), dtype=torch.float64, device=dv)
+            c = torch.empty((2, n, m), dtype=torch.float64, device=dv) if gga else None
+            for s in range(2):
+                b = hc[s, 0][:, None] * a0
+                if gga:
+                    for k in range(1, 4):
+                        b = b + hc[s, k][:, None] * ao[k, g0:g1]
+                    eng._gemm(0, 1, n, m, n, 1.0, dms[s], n, a0, n, 0.0, c[s], m)       # c_s^T = D_s phi^T
+                eng._gemm(0, 1, n, m, n, 1.0, dms[s], n, b.contiguous(), n, 0.0, e[s], m)   # e_s^T = D_s b_s^T
+            if stats is not None:
+                torch.cuda.synchronize(dv)
+                tg += time.perf_counter() - t0
+                t0 = time.perf_counter()
+            _capi.check(L.xt_grad_xc(m, coords[g0:g1].data_ptr(), nshell, t_info.data_ptr(), t_dat.data_ptr(),
+                                     t_sph.data_ptr(), t_nrm.data_ptr(), t_atom.data_ptr(), lmax, natm, n, 2,
+                                     _capi.XC["GGA" if gga else "LDA"], hc.data_ptr(), e.data_ptr(),
+                                     c.data_ptr() if gga else None, m, work.data_ptr(), nwork, out.data_ptr(), st),
+                        "xt_grad_xc")
+            if stats is not None:
+                torch.cuda.synchronize(dv)
+                tk += time.perf_counter() - t0
+                nbytes += 8 * m * (2 * n * (2 if gga else 1) + (6 if gga else 0))
+        if stats is not None:
+            stats.update(gemm_s=tg, grad_xc_s=tk, grad_xc_bytes=nbytes, chunk=chunk, ngrid=ng,
+                         chunks=(ng + chunk - 1) // chunk)
+        return -2.0 * out.cpu().numpy()
+
+
+def ks_ground_terms(d0a, d0b, hyb):
+    """The kernel terms of the UKS two-electron gradient: J[D_a + D_b] with D_a + D_b and, for a
+    hybrid, -hyb K[D_s] with D_s per spin; a pure functional is the J term alone, so
+    ``xt_grad_jk`` forms no exchange contraction."""
+    d0t = d0a + d0b
+    terms = [jk_terms(1, 0, d0t, d0t)]
+    if hyb != 0:
+        terms += [jk_terms(0, -hyb, d0a, d0a), jk_terms(0, -hyb, d0b, d0b)]
+    return terms
+
+
+def check_ks_gradient_mf(mf):
+    """The Kohn-Sham mean fields ``KSGradients`` covers: unrestricted, LDA or GGA (pure or global
+    hybrid), exact integrals, no non-local correlation."""
+    if getattr(mf, "restricted_open", False):
+        raise NotImplementedError("nuclear gradients need a UKS reference: an ROKS determinant is not "
+                                  "variational in the rotations the formula assumes")
+    xc = str(getattr(mf, "xc", "HF"))
+    xctype = _xc.xc_type(xc) if xc.upper() != "HF" else "HF"
+    if xctype == "HF":
+        raise NotImplementedError("KSGradients is for Kohn-Sham mean fields; Hartree-Fock has qc.grad.Gradients")
+    if xctype == "MGGA":
+        raise NotImplementedError(f"nuclear gradients for the meta-GGA {xc!r}: the tau derivative of the XC "
+                                  "potential is not built (LDA / GGA only)")
+    if xctype not in ("LDA", "GGA"):
+        raise NotImplementedError(f"nuclear gradients for xc = {xc!r} of type {xctype}")
+    if _xc.rsh_and_hybrid_coeff(xc)[0] != 0:
+        raise NotImplementedError(f"nuclear gradients for the range-separated {xc!r}: xt_grad_jk has no "
+                                  "long-range (erf) operator")
+    if getattr(mf, "nlc", None) is not None:
+        raise NotImplementedError("nuclear gradients with VV10 non-local correlation: its derivative is not built")
+    if getattr(mf, "with_df", None) is not None:
+        raise NotImplementedError("nuclear gradients for density-fitted mean fields")
+    if getattr(mf, "with_x2c", None) is not None:
+        raise NotImplementedError("nuclear gradients with the X2C core Hamiltonian")
+    uses_chol = getattr(mf, "cderi_exact", None) is not None or getattr(mf, "eri_mode", "") == "cholesky"
+    if uses_chol and float(getattr(mf, "chol_tol", 0.0)) > MAX_CHOL_TOL:
+        raise ValueError(f"nuclear gradients need J / K of the exact integrals: Cholesky tolerance "
+                         f"{mf.chol_tol:g} is above {MAX_CHOL_TOL:g}")
+
+
+class KSGradients(Gradients):
+    """``UKS.nuc_grad_method()`` after ``to_device()``: the one-electron and overlap terms with the
+    energy-weighted density of the Kohn-Sham Fock matrix, J - hyb K through ``xt_grad_jk`` and the
+    XC term through ``xt_grad_xc``.  The grid does not move with the nuclei (``grid_response`` is
+    False and cannot be switched on): the result is the exact derivative of the energy on a grid
+    whose points and weights are held fixed, and it differs from the derivative on an
+    atom-centred grid by the weight derivatives, which vanish with the grid error."""
+
+    def __init__(self, mf):
+        check_ks_gradient_mf(mf)
+        self.base = mf
+        self.mol = mf.mol
+        self.atmlst = None
+        self.de = None
+        self.de_xc = None        # the XC part of the last gradient, (natm, 3)
+        self.timings = {}
+        self.xc_chunk = None     # grid points per xt_grad_xc call; None: default_xc_chunk
+
+    @property
+    def grid_response(self):
+        return False
+
+    @grid_response.setter
+    def grid_response(self, on):
+        if on:
+            raise NotImplementedError("grid_response = True: the derivatives of the grid weights are not built")
+
+    def grad_elec(self, atmlst=None):
+        mf, mol = self.base, self.mol
+        if mf.mo_coeff is None:
+            raise RuntimeError("run the SCF first")
+        dev = self._device()
+        if getattr(mf, "device_engine", None) is None:
+            raise RuntimeError("the XC gradient runs on the GPU (xt_grad_xc): run the SCF after mf.to_device()")
+        orboa, _, orbob, _, fa, fb = uhf_orbitals(mf)      # mf._veff of a UKS is V_xc + J - hyb K
+        nocca, noccb = orboa.shape[1], orbob.shape[1]
+        d0a, d0b = orboa @ orboa.T, orbob @ orbob.T
+        w = orboa @ fa[:nocca, :nocca] @ orboa.T + orbob @ fb[:noccb, :noccb] @ orbob.T
+        t0 = time.perf_counter()
+        de = contract_1e(mol, hcore_generator(mol), get_ovlp(mol), d0a + d0b, w)
+        self.timings["one_electron_s"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        st = {}
+        de += grad_jk_device(mol, ks_ground_terms(d0a, d0b, mf.hyb), dev, stats=st)
+        self.timings["grad_jk_s"] = time.perf_counter() - t0
+        self.timings["buckets"] = st.get("buckets", [])
+        t0 = time.perf_counter()
+        sx = {}
+        self.de_xc = grad_xc_device(mf, d0a, d0b, chunk=self.xc_chunk, stats=sx)
+        de += self.de_xc
+        self.timings["grad_xc_call_s"] = time.perf_counter() - t0
+        self.timings.update(sx)
+        return de if atmlst is None else de[list(atmlst)]

@@ -117,9 +117,13 @@ class _SCFBase:
 
     def nuc_grad_method(self):
         """Analytic nuclear gradient of the converged mean field (PySCF ``mf.nuc_grad_method()``):
-        UHF only (``qc.grad.Gradients``); ROHF / ROKS, a functional and density fitting raise
-        NotImplementedError."""
-        from .grad import Gradients
+        UHF (``qc.grad.Gradients``) and, after ``to_device()``, UKS with an LDA / GGA functional,
+        pure or global hybrid (``qc.grad.KSGradients``: the XC derivative has no host path).  ROHF /
+        ROKS, a functional on the host, meta-GGA, range-separated and VV10 functionals, density
+        fitting and X2C raise NotImplementedError."""
+        from .grad import Gradients, KSGradients
+        if str(self.xc).upper() != "HF" and self._device is not None:
+            return KSGradients(self)
         return Gradients(self)
 
     def _use_cholesky(self):
