@@ -614,6 +614,31 @@ int xt_grad_xc(int ngrid, const double* coords, int nshell, const int* shell_inf
                const int* shell_atom, int lmax, int natm, int nao, int nspin, int xctype,
                const double* h, const double* e, const double* c, long ldg, double* work, long nwork,
                double* out, void* hip_stream);
+/* The exchange-correlation linear response of a UKS reference in the AO route, everything that is
+   not a GEMM (xtddft_amd/qc/device.py DeviceEngine.fxc_response: the XC part of the UKS
+   gen_response(hermi=1) of the Z-vector equations and the f^xc[T] of the spin-flip TDA gradient).
+   For symmetric trial densities dm_s, with c_s = phi dm_s formed by the caller (one GEMM per spin):
+     rho1_s(0, g) = sum_mu phi_mu(g) c_s(g, mu),   rho1_s(k, g) = 2 sum_mu d_k phi_mu(g) c_s(g, mu)
+     wv_s(k, g)   = w_g sum_{s' k'} fxc(s, k, s', k', g) rho1_s'(k', g)       ("eff" layout, nothing halved)
+     b_s(g, mu)   = 1/2 wv_s(0, g) phi_mu(g) + sum_k wv_s(k, g) d_k phi_mu(g)  (XT_XC_GGA)
+     b_s(g, mu)   = wv_s(0, g) phi_mu(g)                                       (XT_XC_LDA)
+   so that V^resp_s = phi^T b_s (GGA: plus its transpose).  Device pointers, ncomp = 1 (LDA) or 4 (GGA):
+     ao[k ao_plane + g ldao + mu]    k = 0 (value) or 0..3 (value, d/dx, d/dy, d/dz); LDA reads plane 0 only
+     c[(s ngrid + g) ldc + mu]       c_s = phi dm_s
+     fxc[((s ncomp + k) 2 ncomp + s' ncomp + k') ldg + g]   as eval_xc_eff returns it, g innermost
+     w[g]                            grid weights
+     rho1[(4 s + k) ldo + g], wv[(4 s + k) ldo + g]   outputs; LDA writes plane k = 0 only
+     b[(s ngrid + g) ldb + mu]       output
+   Any of rho1, wv, b may be null: that output is skipped (all three null: nothing is launched).  A
+   block owns 64 consecutive grid points; no atomics, the summation order is fixed and does not depend
+   on the alignment of the operands, so equal inputs give equal bits.  A point whose fxc entries are
+   all zero gets wv = 0 and b = 0 provided c is finite there.  ngrid = 0 or nao = 0 returns 0 without
+   a launch.  XT_ERR_ARG before any HIP call: negative sizes, ldao / ldc / ldb < nao, ldg / ldo <
+   ngrid, ao_plane shorter than one plane's rows (GGA), xctype not LDA / GGA, more than 2^31 blocks,
+   a null ao, c, fxc or w. */
+int xt_xc_resp(long ngrid, int nao, int xctype, const double* ao, long ao_plane, long ldao,
+               const double* c, long ldc, const double* fxc, long ldg, const double* w,
+               double* rho1, double* wv, long ldo, double* b, long ldb, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -33,7 +33,7 @@ EXPORTS = [
     "xt_int3c2e_cart", "xt_int2e_cart", "xt_eval_ao", "xt_tdm", "xt_tdm_sc", "xt_gemm_plan", "xt_gemm_run",
     "xt_set_nlc", "xt_vv10_ground", "xt_vv10_response",
     "xt_stda_charges", "xt_stda_half", "xt_stda_diag", "xt_stda_select", "xt_stda_matrix",
-    "xt_si_couple", "xt_hint_cart", "xt_grad_jk", "xt_grad_xc",
+    "xt_si_couple", "xt_hint_cart", "xt_grad_jk", "xt_grad_xc", "xt_xc_resp",
 ]
 
 
@@ -175,6 +175,8 @@ def lib():
                              c_int, c_int, dp, c_long, dp, vp]
     L.xt_grad_xc.argtypes = [c_int, dp, c_int, vp, dp, dp, dp, vp, c_int, c_int, c_int, c_int, c_int, dp, dp, dp,
                              c_long, dp, c_long, dp, vp]
+    L.xt_xc_resp.argtypes = [c_long, c_int, c_int, dp, c_long, c_long, dp, c_long, dp, c_long, dp, dp, dp, c_long,
+                             dp, c_long, vp]
     L.xt_eval_ao.argtypes = [c_int, dp, c_int, vp, dp, dp, dp, c_int, dp, c_long, c_long, vp]
     L.xt_tdm.argtypes = [POINTER(XtTdmDesc), dp, dp, dp, dp, dp, dp, c_int, vp]
     L.xt_tdm_sc.argtypes = [POINTER(XtTdmScDesc), dp, dp, dp, dp, dp, dp, dp, c_int, vp]

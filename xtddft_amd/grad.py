@@ -1,4 +1,4 @@
-"""Analytic nuclear gradients of spin-flip TDA (CIS) states on a UHF reference: the reference's
+"""Analytic nuclear gradients of spin-flip TDA (CIS) states on a UHF or UKS reference: the reference's
 USF-CIS gradient (``xtddft/grad_jp/grad/usfcis.py``) with its API,
 
     g = SF_TDA_down(mf).nuc_grad_method()      # or SF_TDA_up(mf)
@@ -18,8 +18,18 @@ Spin-flip-up is the same derivation with alpha and beta exchanged (J / K of a Ha
 reference do not tell the spins apart): the driver hands the spin-reversed orbitals to the
 same function.
 
-Hartree-Fock only: a functional (kernel-derivative terms), density fitting (as the reference,
-usfcis.py:284), an ROHF reference and method != 0 raise NotImplementedError.
+On a UKS reference (LDA / GGA, pure or global hybrid, after ``to_device()``) the same function gives
+the collinear (``method = 2``) spin-flip TDA gradient, the content of the reference's
+``grad_hb/tduks_sfu.py:184-369`` with f1vo = k1ao = 0: every K carries ``hyb``, f^xc[T] joins
+``veff0doo``, the Z-vector operator is the UKS response (``qc.grad.ks_response``: J - hyb K +
+V^resp through ``xt_xc_resp``) and the XC nuclear-derivative term is
+G_xc[w vxc[rho0]; D0 + T + Z^S] + G_xc[wv[T + Z^S]; D0] (``qc.grad.grad_xc_pairs``), on a grid held
+fixed in space.
+
+Refused with NotImplementedError: on a UHF reference method != 0; on a UKS reference method = 0
+(the ALDA0 kernel's density derivative) and method = 1 (third derivatives of the multicollinear
+kernel), a mean field on the host, and everything ``qc.grad.check_ks_gradient_mf`` refuses
+(meta-GGA, range-separated, VV10, ROKS); density fitting, X2C and an ROHF reference on either.
 """
 from __future__ import annotations
 
@@ -31,19 +41,36 @@ from .qc import grad as _g
 
 
 def _scf_of(td):
+    """(the SCF object behind ``td.mf``, whether it is a Kohn-Sham reference) after every refusal."""
     mf = td.mf
     if getattr(mf, "is_rohf", False):
-        raise NotImplementedError("spin-flip gradients need a UHF reference (the reference's "
-                                  "usfcis-rohf.py is not a working code path)")
+        raise NotImplementedError("spin-flip gradients need a UHF / UKS reference (the reference's "
+                                  "usfcis-rohf.py is not a working code path; tdroks_sfu.py is not built)")
     ref = mf.extra.get("qc_scf") if hasattr(mf, "extra") else None
     scf = ref() if ref is not None else None          # a weak reference: the mean field does not own the SCF
     if scf is None:
         if str(getattr(mf, "xctype", "HF")) != "HF":
-            raise NotImplementedError(f"spin-flip gradients for xc = {mf.xc!r}: Hartree-Fock only")
+            raise NotImplementedError(f"spin-flip gradients for xc = {mf.xc!r} need the qc UKS object the mean "
+                                      "field came from (UKS.to_meanfield()), still alive")
         raise ValueError("the gradient needs the SCF object the mean field came from (qc UHF.to_meanfield()), "
                          "still alive")
-    _g.check_gradient_mf(scf)
-    return scf
+    if str(getattr(scf, "xc", "HF")).upper() == "HF":
+        if td.method != 0:
+            raise NotImplementedError("spin-flip gradients on a Hartree-Fock reference are built for method = 0 only")
+        _g.check_gradient_mf(scf)
+        return scf, False
+    if getattr(scf, "_device", None) is None:
+        raise NotImplementedError(f"spin-flip gradients for xc = {scf.xc!r} on the host: the XC derivative "
+                                  "(xt_grad_xc) and the XC response (xt_xc_resp) have no host path; call "
+                                  "mf.to_device() before the SCF")
+    _g.check_ks_gradient_mf(scf)
+    if td.method == 0:
+        raise NotImplementedError("spin-flip gradients with the ALDA0 kernel (method = 0) on a functional: the "
+                                  "density derivative of the ALDA0 kernel is not built (method = 2 is)")
+    if td.method == 1:
+        raise NotImplementedError("spin-flip gradients with the multicollinear kernel (method = 1): its third "
+                                  "functional derivatives are not built (method = 2 is)")
+    return scf, True
 
 
 def sf_amplitude(td, state_idx):
@@ -63,15 +90,76 @@ def sf_amplitude(td, state_idx):
     return x.T / np.linalg.norm(x)
 
 
-def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None):
-    """Electronic part of the gradient of E_UHF + omega, (natm, 3).  ``x_ab`` (nvir_b, nocc_a) in
-    the labels of spin-flip-down; ``flip``: the state is spin-flip-up, and "a" below is beta."""
+class KSTerms:
+    """The XC hook of ``grad_elec`` for a UKS reference (LDA / GGA, collinear kernel): the response
+    potential V^resp of the reference (``DeviceEngine.fxc_response``) and the XC nuclear-derivative
+    terms (``qc.grad.grad_xc_pairs``).  ``grad_elec`` works in the labels "a" = flipped-from,
+    "b" = flipped-to; the engine keeps alpha, beta, so every density pair is put into the engine's
+    order on the way in and every potential back on the way out (``s``)."""
+
+    def __init__(self, scf, s, timings, xc_chunk=None):
+        self.scf, self.s, self.tm = scf, s, timings
+        self.eng = scf.device_engine
+        if self.eng is None:
+            raise RuntimeError("the XC terms run on the GPU: run the SCF after mf.to_device()")
+        self.xc_chunk = xc_chunk
+        self.de_xc = None        # the XC nuclear-derivative part, set by grad()
+        self._ks = _g.ks_response(scf)
+        self.tm["xc_response_s"] = 0.0
+        self.tm["xc_response_calls"] = 0
+
+    def _order(self, pair):
+        return np.asarray([pair[self.s[0]], pair[self.s[1]]])     # s is its own inverse
+
+    def _timed(self, f, *a, **kw):
+        t0 = time.perf_counter()
+        out = f(*a, **kw)
+        self.tm["xc_response_s"] += time.perf_counter() - t0
+        self.tm["xc_response_calls"] += 1
+        return out
+
+    def vxc_resp(self, dm):
+        """V^resp (2, nao, nao) of a symmetric density pair, in the labels of ``grad_elec``."""
+        return self._order(self._timed(self.eng.fxc_response, self._order(dm), want=("v",))["v"])
+
+    def vresp(self, dm):
+        """J[dm_a + dm_b] - hyb K[dm_s] + V^resp_s[dm]: what the Z-vector equations apply."""
+        t0 = time.perf_counter()
+        out = self._order(self._ks(self._order(dm)))
+        self.tm["xc_response_s"] += time.perf_counter() - t0     # J / K included: one call of the response
+        self.tm["xc_response_calls"] += 1
+        return out
+
+    def grad(self, d0, tz):
+        """G_xc[w vxc[rho0]; D0 + T + Z^S] + G_xc[wv[T + Z^S]; D0], (natm, 3); d0, tz in the labels of
+        ``grad_elec``."""
+        import torch
+        from .qc import xc as _xc
+        eng = self.eng
+        d0, tz = self._order(d0), self._order(tz)
+        wv = self._timed(eng.fxc_response, tz, want=("wv",))["wv"]
+        t0 = time.perf_counter()
+        with torch.cuda.device(eng.dev):
+            h0 = _xc.eval_xc_eff_torch(self.scf.xc, eng.rho(d0), deriv=1)[1] * eng.w
+        st = {}
+        de = _g.grad_xc_pairs(self.scf, [(h0, d0 + tz), (wv, d0)], chunk=self.xc_chunk, stats=st)
+        self.tm["grad_xc_s"] = time.perf_counter() - t0
+        self.tm["grad_xc_stats"] = st
+        self.de_xc = de
+        return de
+
+
+def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None, hyb=1.0, xc=None):
+    """Electronic part of the gradient of E_SCF + omega, (natm, 3).  ``x_ab`` (nvir_b, nocc_a) in
+    the labels of spin-flip-down; ``flip``: the state is spin-flip-up, and "a" below is beta.
+    ``hyb``: the fraction of exact exchange (1 for Hartree-Fock) on every K; ``xc``: the XC terms of a
+    UKS reference (``KSTerms``), None for Hartree-Fock, which then runs exactly the UHF formula."""
     tm = {} if timings is None else timings
     mol = scf.mol
     s = (1, 0) if flip else (0, 1)
     mo_coeff = [scf.mo_coeff[s[0]], scf.mo_coeff[s[1]]]
     mo_occ = [scf.mo_occ[s[0]], scf.mo_occ[s[1]]]
-    fock_ao = scf.get_hcore()[None] + np.asarray(scf._veff)
+    fock_ao = scf.get_hcore()[None] + np.asarray(scf._veff)       # a UKS _veff holds V_xc
     orboa, orbva = mo_coeff[0][:, mo_occ[0] > 0], mo_coeff[0][:, mo_occ[0] == 0]
     orbob, orbvb = mo_coeff[1][:, mo_occ[1] > 0], mo_coeff[1][:, mo_occ[1] == 0]
     nocca, noccb = orboa.shape[1], orbob.shape[1]
@@ -81,7 +169,11 @@ def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, 
         raise ValueError(f"amplitude shape {x_ab.shape}, expected {(orbvb.shape[1], nocca)}")
 
     def get_jk(dms):             # J / K do not depend on which spin a density belongs to
-        return scf.get_jk(dm=np.asarray(dms), hermi=0)
+        dms = np.asarray(dms)
+        if hyb == 0:             # a pure functional forms no exchange
+            return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], np.zeros_like(dms)
+        vj, vk = scf.get_jk(dm=dms, hermi=0)
+        return vj, (vk if hyb == 1 else hyb * vk)
 
     # T_alpha (occupied-occupied), T_beta (virtual-virtual), X in the AO basis
     ta = -x_ab.T @ x_ab
@@ -90,21 +182,28 @@ def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, 
     dmtb = orbvb @ tb @ orbvb.T
     dmxab = orbvb @ x_ab @ orboa.T
     dmSx, dmAx = (dmxab + dmxab.T) / 2, (dmxab - dmxab.T) / 2
-    vj, vk = get_jk((dmta, dmtb, dmSx, dmAx))
+    vj, vk = get_jk((dmta, dmtb, dmSx, dmAx))                     # vk carries hyb from here on
     vkmo = mo_coeff[1].T @ (vk[2] + vk[3]) @ mo_coeff[0]          # K[X_S] + K[X_A]: beta rows, alpha columns
     veff0dooa = vj[0] + vj[1] - vk[0]
     veff0doob = vj[0] + vj[1] - vk[1]
+    if xc is not None:           # f^xc[T]
+        fxt = xc.vxc_resp(((dmta + dmta.T) * 0.5, (dmtb + dmtb.T) * 0.5))
+        veff0dooa, veff0doob = veff0dooa + fxt[0], veff0doob + fxt[1]
     # right-hand side of the Z-vector equations
     wvoa = 2.0 * (orbva.T @ veff0dooa @ orboa + fockamo[nocca:, :nocca] @ ta.T - vkmo[noccb:, nocca:].T @ x_ab)
     wvob = 2.0 * (orbvb.T @ veff0doob @ orbob - tb @ fockbmo[:noccb, noccb:].T + x_ab @ vkmo[:noccb, :nocca].T)
     t0 = time.perf_counter()
-    za, zb, res, ncyc = _g.solve_zvector(_SpinView(scf, s), wvoa, wvob, cphf_conv_tol, cphf_max_cycle)
+    za, zb, res, ncyc = _g.solve_zvector(_SpinView(scf, s), wvoa, wvob, cphf_conv_tol, cphf_max_cycle,
+                                         vresp=None if xc is None else xc.vresp)
     tm["zvector_s"] = time.perf_counter() - t0
     tm["zvector_cycles"], tm["zvector_residual"] = ncyc, float(res)
     z1ao = np.asarray([orbva @ za @ orboa.T, orbvb @ zb @ orbob.T])
     zs = (z1ao + z1ao.transpose(0, 2, 1)) * 0.5
-    vjz, vkz = get_jk(zs)
-    veff = (vjz[0] + vjz[1])[None] - vkz
+    if xc is None:
+        vjz, vkz = get_jk(zs)
+        veff = (vjz[0] + vjz[1])[None] - vkz
+    else:
+        veff = xc.vresp(zs)      # J - hyb K + V^resp[Z^S]
     # energy-weighted density W
     im0a = np.zeros_like(fockamo)
     im0b = np.zeros_like(fockbmo)
@@ -124,16 +223,19 @@ def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, 
     # two-electron part: ground state + (T + Z^S) cross terms as D x D - TZ x TZ, and X_S, X_A
     da, db = oo0a + dmz1dooa, oo0b + dmz1doob
     tz = dmz1dooa + dmz1doob
-    terms = [_g.jk_terms(1, 0, da + db, da + db), _g.jk_terms(-1, 0, tz, tz),
-             _g.jk_terms(0, -1, da, da), _g.jk_terms(0, 1, dmz1dooa, dmz1dooa),
-             _g.jk_terms(0, -1, db, db), _g.jk_terms(0, 1, dmz1doob, dmz1doob),
-             _g.jk_terms(0, -2, dmSx, dmSx),
-             (0.0, 2.0, dmAx - dmAx.T, dmAx)]       # -2 vk[X_A] . (X_A[p,q] - X_A[q,p])
+    terms = [_g.jk_terms(1, 0, da + db, da + db), _g.jk_terms(-1, 0, tz, tz)]
+    if hyb != 0:
+        terms += [_g.jk_terms(0, -hyb, da, da), _g.jk_terms(0, hyb, dmz1dooa, dmz1dooa),
+                  _g.jk_terms(0, -hyb, db, db), _g.jk_terms(0, hyb, dmz1doob, dmz1doob),
+                  _g.jk_terms(0, -2 * hyb, dmSx, dmSx),
+                  (0.0, 2.0 * hyb, dmAx - dmAx.T, dmAx)]       # -2 hyb vk[X_A] . (X_A[p,q] - X_A[q,p])
     t0 = time.perf_counter()
     st = {}
     de += _g.grad_jk_device(mol, terms, device, stats=st)
     tm["grad_jk_s"] = time.perf_counter() - t0
     tm["buckets"] = st.get("buckets", [])
+    if xc is not None:
+        de += xc.grad((oo0a, oo0b), (dmz1dooa, dmz1doob))
     return de
 
 
@@ -157,20 +259,24 @@ class _SpinView:
 class SFGradients:
     """``SF_TDA_down(mf).nuc_grad_method()`` / ``SF_TDA_up(mf).nuc_grad_method()`` with the
     reference's attributes (usfcis.py:261-331): ``state`` (1-based), ``cphf_conv_tol``,
-    ``cphf_max_cycle`` (the values its solver actually runs with, usfcis.py:145-148), ``atmlst``."""
+    ``cphf_max_cycle`` (the values its solver actually runs with, usfcis.py:145-148), ``atmlst``.
+    A UHF reference takes method = 0; a UKS reference (LDA / GGA, pure or global hybrid, on a device)
+    takes the collinear kernel, method = 2.  ``timings`` of the last gradient: ``one_electron_s``,
+    ``grad_jk_s``, ``zvector_s`` / ``zvector_cycles`` / ``zvector_residual`` and, for a UKS reference,
+    ``xc_response_s`` (every V^resp / wv evaluation, the Z-vector's included), ``grad_xc_s``."""
 
     cphf_max_cycle = 500
     cphf_conv_tol = 1e-10
 
     def __init__(self, td):
-        if td.method != 0:
-            raise NotImplementedError("spin-flip gradients are built for method = 0 only")
         self.base = td
-        self._scf = _scf_of(td)
+        self._scf, self.is_ks = _scf_of(td)
         self.mol = self._scf.mol
         self.state = 1
         self.atmlst = None
         self.de = None
+        self.de_xc = None        # the XC nuclear-derivative part of the last gradient (UKS reference)
+        self.xc_chunk = None     # grid points per xt_grad_xc call; None: qc.grad.default_xc_chunk
         self.timings = {}
 
     def grad_nuc(self, mol=None, atmlst=None):
@@ -189,8 +295,16 @@ class SFGradients:
         if dev is None:
             raise RuntimeError("the gradient runs on the GPU (xt_grad_jk, device J / K): call "
                                "mf.to_device() before the SCF")
-        de = grad_elec(self._scf, sf_amplitude(td, self.state - 1), td.isf == 1, dev, self.cphf_conv_tol,
-                       self.cphf_max_cycle, self.timings)
+        flip = td.isf == 1
+        if self.is_ks:
+            self.timings.clear()
+            xc = KSTerms(self._scf, (1, 0) if flip else (0, 1), self.timings, self.xc_chunk)
+            de = grad_elec(self._scf, sf_amplitude(td, self.state - 1), flip, dev, self.cphf_conv_tol,
+                           self.cphf_max_cycle, self.timings, hyb=float(self._scf.hyb), xc=xc)
+            self.de_xc = xc.de_xc
+        else:
+            de = grad_elec(self._scf, sf_amplitude(td, self.state - 1), flip, dev, self.cphf_conv_tol,
+                           self.cphf_max_cycle, self.timings)
         return de if atmlst is None else de[list(atmlst)]
 
     def kernel(self, state=None, atmlst=None):

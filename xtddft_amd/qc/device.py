@@ -207,6 +207,102 @@ class DeviceEngine:
                 vm.append(self._mm(ao[0], (wv[0][:, None] * ao[0]).contiguous(), ta=1))
         return e, torch.stack(vm).cpu().numpy()
 
+    # ------------------------------------------------------------ XC linear response (AO route)
+    _fxc = None           # (fxc (2, ncomp, 2, ncomp, G) on the device, the density it belongs to)
+    fxc_chunk = None      # grid points per xt_xc_resp call; None: the byte budget of qc.grad.default_xc_chunk
+
+    def fxc_ground(self, dm0=None):
+        """The second functional derivative at the SCF spin densities ``dm0`` (2, nao, nao), on the
+        device: evaluated once per engine and kept (a rebuilt mean field has a new engine); a call
+        with another density evaluates it anew.  ``dm0`` None: the kept one."""
+        if self.xctype not in ("LDA", "GGA"):
+            raise NotImplementedError(f"the AO-route XC response covers LDA / GGA functionals, not {self.xctype}")
+        if dm0 is not None:
+            dm0 = np.ascontiguousarray(np.asarray(dm0, dtype=np.float64))
+        if self._fxc is None or (dm0 is not None and not np.array_equal(dm0, self._fxc[1])):
+            if dm0 is None:
+                raise RuntimeError("fxc_response needs fxc_ground(dm0) at the SCF density first")
+            fxc = _xc.eval_xc_eff_torch(self.xc, self.rho(dm0), deriv=2)[2].contiguous()
+            self._fxc = (fxc, dm0.copy())
+        return self._fxc[0]
+
+    def fxc_response(self, dms, want=("v",), stats=None):
+        """The XC linear response of the UKS reference to symmetric trial densities ``dms``
+        (2, nao, nao), with the kernel of ``fxc_ground``: per grid chunk the GEMMs c_s = phi dm_s, one
+        ``xt_xc_resp`` call (rho1, wv = w fxc rho1 and b_s, csrc/xt_xc_resp.hip) and the GEMMs
+        phi^T b_s.  ``want``: "v" -- the response potential V^resp (2, nao, nao), a host array, phi^T b
+        plus its transpose for GGA (the conventions of ``vxc``); "wv" -- the unhalved weights
+        (2, 4, G) on the device, planes 1..3 zero for LDA.  Returns a dict.  ``stats`` receives the
+        seconds of the GEMMs and of the kernel and the bytes the kernel moved."""
+        import time
+        torch = self.torch
+        unknown = set(want) - {"v", "wv"}
+        if unknown or not want:
+            raise ValueError(f"fxc_response: want is any of 'v', 'wv', got {tuple(want)}")
+        fxc = self.fxc_ground()
+        from .grad import default_xc_chunk
+        gga = self.xctype == "GGA"
+        n, ao = self.n, self.ao
+        ng = int(self.w.shape[0])
+        chunk = default_xc_chunk(n, ng) if self.fxc_chunk is None else int(self.fxc_chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        need_v, need_wv = "v" in want, "wv" in want
+        d = torch.as_tensor(np.ascontiguousarray(np.asarray(dms, dtype=np.float64)), device=self.dev)
+        if d.shape != (2, n, n):
+            raise ValueError(f"fxc_response: densities of shape {tuple(d.shape)}, expected {(2, n, n)}")
+        kw = dict(dtype=torch.float64, device=self.dev)
+        wv = torch.zeros((2, 4, ng), **kw) if need_wv else None
+        v = torch.zeros((2, n, n), **kw) if need_v else None
+        tg = tk = 0.0
+        nbytes = 0
+        with torch.cuda.device(self.dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+            for g0 in range(0, ng, chunk):
+                g1 = min(ng, g0 + chunk)
+                m = g1 - g0
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    t0 = time.perf_counter()
+                a0 = ao[0, g0:g1]
+                c = torch.empty((2, m, n), **kw)
+                for s in range(2):
+                    self._gemm(0, 0, m, n, n, 1.0, a0, n, d[s], n, 0.0, c[s], n)        # c_s = phi dm_s
+                b = torch.empty((2, m, n), **kw) if need_v else None
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    tg += time.perf_counter() - t0
+                    t0 = time.perf_counter()
+                _capi.check(self.L.xt_xc_resp(m, n, _capi.XC[self.xctype], a0.data_ptr(), ao.stride(0), n,
+                                              c.data_ptr(), n, fxc[..., g0:].data_ptr(), ng, self.w[g0:].data_ptr(),
+                                              None, wv[..., g0:].data_ptr() if need_wv else None, ng,
+                                              b.data_ptr() if need_v else None, n, st), "xt_xc_resp")
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    tk += time.perf_counter() - t0
+                    t0 = time.perf_counter()
+                    ncomp = 4 if gga else 1
+                    # ao and c once for rho1; with b: ao once more, b once; fxc, w, wv
+                    nbytes += 8 * m * ((ncomp + 2) * n * (2 if need_v else 1)
+                                       + 4 * ncomp * ncomp + 1 + (2 * ncomp if need_wv else 0))
+                if need_v:
+                    for s in range(2):
+                        self._gemm(1, 0, n, n, m, 1.0, a0, n, b[s], n, 1.0, v[s], n)    # v_s += phi^T b_s
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    tg += time.perf_counter() - t0
+        if stats is not None:
+            stats.update(gemm_s=tg, xc_resp_s=tk, xc_resp_bytes=nbytes, chunk=chunk, ngrid=ng,
+                         chunks=(ng + chunk - 1) // chunk)
+        out = {}
+        if need_v:
+            if gga:
+                v = v + v.transpose(1, 2)
+            out["v"] = v.cpu().numpy()
+        if need_wv:
+            out["wv"] = wv
+        return out
+
     def kernels(self, dms):
         """(fxc (2, ncomp, 2, ncomp, G), ALDA0 fxc_ab (G)) at the SCF density:
         cache_xc_kernel (XTDA.py:504) and cache_xc_kernel_sf (SF_TDA.py:69-85)."""

@@ -28,7 +28,13 @@
   with h_s = w vxc_s in the "eff" layout (d eps / d rho_s, d eps / d(d_k rho_s); nothing halved),
   b_s = h_s[0] phi + sum_k h_s[k] d_k phi, e_s = b_s D_s and c_s = phi D_s;
 * ``KSGradients`` -- ``UKS.nuc_grad_method()`` after ``to_device()``: LDA / GGA functionals, pure
-  and global hybrid, without grid-weight derivatives (``grid_response = False``).
+  and global hybrid, without grid-weight derivatives (``grid_response = False``);
+* ``grad_xc_pairs`` -- the same bracket for any list of (weights h, densities D): G_xc[h; D] is
+  bilinear, and the excited-state gradients of ``xtddft_amd/grad.py`` need it at
+  (w vxc[rho0], D0 + T + Z^S) and at (wv[T + Z^S], D0);
+* ``ks_response`` -- the response of a UKS mean field to a symmetric density pair,
+  J - hyb K + V^resp (``DeviceEngine.fxc_response``, kernel ``xt_xc_resp``), which ``solve_zvector``
+  takes through its ``vresp`` argument.
 """
 from __future__ import annotations
 
@@ -320,13 +326,37 @@ def hf_response(mf):
     return vresp
 
 
-def solve_zvector(mf, wvoa, wvob, tol=1e-10, max_cycle=500):
+def ks_response(mf):
+    """vresp(dm (2, nao, nao) symmetric) = J[dm_a + dm_b] - hyb K[dm_s] + V^resp_s[dm]
+    (``mf.gen_response(hermi=1)`` of a UKS mean field, LDA / GGA, global hybrid or pure): J / K from
+    ``mf.get_jk`` and the XC response from ``DeviceEngine.fxc_response`` with fxc at the SCF
+    density.  A pure functional forms no exchange."""
+    eng = getattr(mf, "device_engine", None)
+    if eng is None:
+        raise RuntimeError("ks_response needs a built Kohn-Sham mean field on a device (mf.to_device())")
+    hyb = float(mf.hyb)
+    eng.fxc_ground(np.asarray(mf.make_rdm1()))
+
+    def vresp(dm):
+        dm = np.asarray(dm)
+        vxc = eng.fxc_response(dm, want=("v",))["v"]
+        if hyb != 0:
+            vj, vk = mf.get_jk(dm=dm, hermi=1)
+            return (vj[0] + vj[1])[None] - hyb * vk + vxc
+        vj = mf.get_jk(dm=dm, hermi=1, with_k=False)[0]
+        return (vj[0] + vj[1])[None] + vxc
+    return vresp
+
+
+def solve_zvector(mf, wvoa, wvob, tol=1e-10, max_cycle=500, vresp=None):
     """z (vo blocks of both spins) with fvind(z) = -(wvoa, wvob) (usfcis.py:126-150): (A + B) of
-    the UHF reference, preconditioned by the orbital-energy differences.  Returns
-    (z1a, z1b, residual, cycles)."""
+    the reference, preconditioned by the orbital-energy differences.  ``vresp``: the response of
+    the mean field to a symmetric density pair, default ``hf_response(mf)`` (a UKS reference passes
+    ``ks_response``).  Returns (z1a, z1b, residual, cycles)."""
     orboa, orbva, orbob, orbvb, fa, fb = uhf_orbitals(mf)
     nocca, nvira, noccb, nvirb = orboa.shape[1], orbva.shape[1], orbob.shape[1], orbvb.shape[1]
-    vresp = hf_response(mf)
+    if vresp is None:
+        vresp = hf_response(mf)
     na = nvira * nocca
 
     def fvind(x):
@@ -461,6 +491,40 @@ def grad_xc_device(mf, d0a, d0b, chunk=None, stats=None):
     e_s = D_s b_s^T and c_s = D_s phi^T run on the engine's FP64 MFMA GEMM in the AO-major layout
     the kernel reads, then one ``xt_grad_xc`` call adds the chunk's force.  ``stats``: a dict that
     receives the seconds of the GEMMs and of the kernel and the bytes of h, e and c it read."""
+    def items(eng, t):
+        dms = t(np.asarray([d0a, d0b], dtype=np.float64))
+        rho = eng.torch.stack([eng._rho(dms[0]), eng._rho(dms[1])])
+        vxc = _xc.eval_xc_eff_torch(mf.xc, rho, deriv=1)[1]
+        return [(vxc * eng.w, dms)]                                              # h: (2, ncomp, G)
+    return _grad_xc_run(mf, items, chunk, stats)
+
+
+def grad_xc_pairs(mf, pairs, chunk=None, stats=None):
+    """(natm, 3): sum over ``pairs`` = [(h, (Da, Db))] of the bracket of ``grad_xc_device`` with the
+    weights h (2, ncomp, G) on the device ("eff" layout, nothing halved) and the densities
+    (Da + Da^T) / 2, (Db + Db^T) / 2 -- G_xc[h; D], bilinear in both.  ``grad_xc_device(mf, d0a, d0b)``
+    is the single pair (w vxc[rho0], D0); the excited-state gradients add (wv[T + Z^S], D0).  The
+    chunk loop runs once per pair and every pair adds into the same (natm, 3) array."""
+    pairs = list(pairs)
+    if not pairs:
+        raise ValueError("grad_xc_pairs needs at least one (h, (Da, Db)) pair")
+
+    def items(eng, t):
+        ng, ncomp = int(eng.w.shape[0]), (4 if mf.xctype == "GGA" else 1)
+        out = []
+        for h, (da, db) in pairs:
+            da, db = np.asarray(da, dtype=np.float64), np.asarray(db, dtype=np.float64)
+            h = eng.torch.as_tensor(h, dtype=eng.torch.float64, device=eng.dev)
+            if h.dim() != 3 or h.shape[0] != 2 or h.shape[1] < ncomp or h.shape[2] != ng:
+                raise ValueError(f"grad_xc_pairs: weights of shape {tuple(h.shape)}, expected (2, >= {ncomp}, {ng})")
+            out.append((h[:, :ncomp], t(np.asarray([(da + da.T) * 0.5, (db + db.T) * 0.5]))))
+        return out
+    return _grad_xc_run(mf, items, chunk, stats)
+
+
+def _grad_xc_run(mf, make_items, chunk, stats):
+    """The chunk loop of ``grad_xc_device`` / ``grad_xc_pairs`` over the (h, densities) items that
+    ``make_items(engine, to_device)`` returns."""
     import torch
     from .dints import _sph_table, ao_shell_tables
     eng = getattr(mf, "device_engine", None)
@@ -479,10 +543,7 @@ def grad_xc_device(mf, d0a, d0b, chunk=None, stats=None):
     with torch.cuda.device(dv):
         def t(x):
             return torch.as_tensor(np.ascontiguousarray(x), device=dv)
-        dms = t(np.asarray([d0a, d0b], dtype=np.float64))
-        rho = torch.stack([eng._rho(dms[0]), eng._rho(dms[1])])
-        vxc = _xc.eval_xc_eff_torch(mf.xc, rho, deriv=1)[1]
-        h = vxc * eng.w                                                          # (2, ncomp, G)
+        items = make_items(eng, t)
         coords = t(np.asarray(mf.grids.coords, dtype=np.float64))
         t_info, t_dat, t_sph, t_nrm = t(info), t(dat), t(_sph_table()), t(mol._norm)
         t_atom = t(np.array([s.atom for s in mol.shells], dtype=np.int32))
@@ -494,37 +555,38 @@ def grad_xc_device(mf, d0a, d0b, chunk=None, stats=None):
         ao = eng.ao
         tg = tk = 0.0
         nbytes = 0
-        for g0 in range(0, ng, chunk):
-            g1 = min(ng, g0 + chunk)
-            m = g1 - g0
-            if stats is not None:
-                torch.cuda.synchronize(dv)
-                t0 = time.perf_counter()
-            hc = torch.zeros((2, 4, m), dtype=torch.float64, device=dv)
-            hc[:, :h.shape[1]] = h[:, :, g0:g1]
-            a0 = ao[0, g0:g1]
-            e = torch.empty((2, n, m), dtype=torch.float64, device=dv)
-            c = torch.empty((2, n, m), dtype=torch.float64, device=dv) if gga else None
-            for s in range(2):
-                b = hc[s, 0][:, None] * a0
-                if gga:
-                    for k in range(1, 4):
-                        b = b + hc[s, k][:, None] * ao[k, g0:g1]
-                    eng._gemm(0, 1, n, m, n, 1.0, dms[s], n, a0, n, 0.0, c[s], m)       # c_s^T = D_s phi^T
-                eng._gemm(0, 1, n, m, n, 1.0, dms[s], n, b.contiguous(), n, 0.0, e[s], m)   # e_s^T = D_s b_s^T
-            if stats is not None:
-                torch.cuda.synchronize(dv)
-                tg += time.perf_counter() - t0
-                t0 = time.perf_counter()
-            _capi.check(L.xt_grad_xc(m, coords[g0:g1].data_ptr(), nshell, t_info.data_ptr(), t_dat.data_ptr(),
-                                     t_sph.data_ptr(), t_nrm.data_ptr(), t_atom.data_ptr(), lmax, natm, n, 2,
-                                     _capi.XC["GGA" if gga else "LDA"], hc.data_ptr(), e.data_ptr(),
-                                     c.data_ptr() if gga else None, m, work.data_ptr(), nwork, out.data_ptr(), st),
-                        "xt_grad_xc")
-            if stats is not None:
-                torch.cuda.synchronize(dv)
-                tk += time.perf_counter() - t0
-                nbytes += 8 * m * (2 * n * (2 if gga else 1) + (6 if gga else 0))
+        for h, dms in items:
+            for g0 in range(0, ng, chunk):
+                g1 = min(ng, g0 + chunk)
+                m = g1 - g0
+                if stats is not None:
+                    torch.cuda.synchronize(dv)
+                    t0 = time.perf_counter()
+                hc = torch.zeros((2, 4, m), dtype=torch.float64, device=dv)
+                hc[:, :h.shape[1]] = h[:, :, g0:g1]
+                a0 = ao[0, g0:g1]
+                e = torch.empty((2, n, m), dtype=torch.float64, device=dv)
+                c = torch.empty((2, n, m), dtype=torch.float64, device=dv) if gga else None
+                for s in range(2):
+                    b = hc[s, 0][:, None] * a0
+                    if gga:
+                        for k in range(1, 4):
+                            b = b + hc[s, k][:, None] * ao[k, g0:g1]
+                        eng._gemm(0, 1, n, m, n, 1.0, dms[s], n, a0, n, 0.0, c[s], m)       # c_s^T = D_s phi^T
+                    eng._gemm(0, 1, n, m, n, 1.0, dms[s], n, b.contiguous(), n, 0.0, e[s], m)   # e_s^T = D_s b_s^T
+                if stats is not None:
+                    torch.cuda.synchronize(dv)
+                    tg += time.perf_counter() - t0
+                    t0 = time.perf_counter()
+                _capi.check(L.xt_grad_xc(m, coords[g0:g1].data_ptr(), nshell, t_info.data_ptr(), t_dat.data_ptr(),
+                                         t_sph.data_ptr(), t_nrm.data_ptr(), t_atom.data_ptr(), lmax, natm, n, 2,
+                                         _capi.XC["GGA" if gga else "LDA"], hc.data_ptr(), e.data_ptr(),
+                                         c.data_ptr() if gga else None, m, work.data_ptr(), nwork, out.data_ptr(), st),
+                            "xt_grad_xc")
+                if stats is not None:
+                    torch.cuda.synchronize(dv)
+                    tk += time.perf_counter() - t0
+                    nbytes += 8 * m * (2 * n * (2 if gga else 1) + (6 if gga else 0))
         if stats is not None:
             stats.update(gemm_s=tg, grad_xc_s=tk, grad_xc_bytes=nbytes, chunk=chunk, ngrid=ng,
                          chunks=(ng + chunk - 1) // chunk)

@@ -194,7 +194,11 @@ class _SFBase:
 
     def nuc_grad_method(self):
         """Analytic nuclear gradient of a root (``xtddft_amd.grad.SFGradients``; the reference's
-        USFTDA.nuc_grad_method, grad_jp/grad/usfcis.py:368): UHF / Hartree-Fock, method 0."""
+        USFTDA.nuc_grad_method, grad_jp/grad/usfcis.py:368, and grad_hb/tduks_sfu.py): on a UHF /
+        Hartree-Fock reference with method 0; on a UKS reference (LDA / GGA, pure or global hybrid,
+        after ``to_device()``) with the collinear kernel, method 2.  Methods 0 and 1 on a functional,
+        a KS mean field on the host and what ``qc.grad.check_ks_gradient_mf`` refuses raise
+        NotImplementedError."""
         from .grad import SFGradients
         return SFGradients(self)
 
