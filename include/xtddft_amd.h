@@ -639,6 +639,34 @@ int xt_grad_xc(int ngrid, const double* coords, int nshell, const int* shell_inf
 int xt_xc_resp(long ngrid, int nao, int xctype, const double* ao, long ao_plane, long ldao,
                const double* c, long ldc, const double* fxc, long ldg, const double* w,
                double* rho1, double* wv, long ldo, double* b, long ldb, void* hip_stream);
+/* The spin-flip channel of the multicollinear kernel in the AO route (DeviceEngine.fxc_sf_response:
+   the f^xc_sf[X] potential and weights of the multicollinear spin-flip TDA gradient).  One channel;
+   with c = phi X_S formed by the caller, X_S the symmetrised transition density:
+     rho1(0, g) = sum_mu phi_mu(g) c(g, mu),   rho1(k, g) = 2 sum_mu d_k phi_mu(g) c(g, mu)
+     wv(k, g)   = 2 w_g sum_k' fxc_sf(k, k', g) rho1(k', g)                   (nothing halved)
+     b(g, mu)   = 1/2 wv(0, g) phi_mu(g) + sum_k wv(k, g) d_k phi_mu(g)       (XT_XC_GGA)
+     b(g, mu)   = wv(0, g) phi_mu(g)                                          (XT_XC_LDA)
+   Device pointers, nk = 1 (LDA) or 4 (GGA):
+     ao[k ao_plane + g ldao + mu], w[g]   as for xt_xc_resp
+     c[g ldc + mu]                        c = phi X_S
+     fxc_sf[(k nk + k') ldg + g]          the multicollinear kernel (mcol.sf_mc_kernel), g innermost
+     rho1[k ldo + g], wv[k ldo + g]       outputs; LDA writes plane 0 only
+     b[g ldb + mu]                        output
+   Any of rho1, wv, b may be null (all three: nothing is launched).  Blocks, summation order, zero
+   weights, zero sizes and the XT_ERR_ARG list are those of xt_xc_resp. */
+int xt_xc_resp_sf(long ngrid, int nao, int xctype, const double* ao, long ao_plane, long ldao,
+                  const double* c, long ldc, const double* fxc_sf, long ldg, const double* w,
+                  double* rho1, double* wv, long ldo, double* b, long ldb, void* hip_stream);
+/* The rows b_ch of given grid weights, nch = 1..4 channels with the AO rows read once for all:
+     b[(ch ngrid + g) ldb + mu] = 1/2 wv(ch, 0, g) phi_mu(g) + sum_k wv(ch, k, g) d_k phi_mu(g)   (XT_XC_GGA)
+     b[(ch ngrid + g) ldb + mu] = wv(ch, 0, g) phi_mu(g)                                          (XT_XC_LDA)
+   with wv[(4 ch + k) ldo + g] (LDA reads plane k = 0 only), so that the potential of the weights is
+   phi^T b_ch (GGA: plus its transpose).  The arithmetic is the third pass of xt_xc_resp: on the wv
+   that call wrote, nch = 2 gives its b bit for bit.  A null b returns 0 without a launch.  XT_ERR_ARG
+   before any HIP call: negative sizes, nch outside 1..4, ldao / ldb < nao, ldo < ngrid, ao_plane
+   shorter than one plane's rows (GGA), xctype not LDA / GGA, more than 2^31 blocks, a null ao or wv. */
+int xt_xc_rows(long ngrid, int nao, int xctype, int nch, const double* ao, long ao_plane, long ldao,
+               const double* wv, long ldo, double* b, long ldb, void* hip_stream);
 
 #ifdef __cplusplus
 }

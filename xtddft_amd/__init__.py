@@ -15,6 +15,9 @@ Reference-compatible entry points (PySCF-style operator API):
 * ``qc.UKS(mol, xc).to_device().nuc_grad_method()``: the UKS ground-state gradient, LDA / GGA,
   pure and global hybrid (the mean-field gradient xtddft/grad_hb/tduks_sfu.py starts from;
   ``xtddft_amd/qc/grad.py`` ``KSGradients``)
+* ``SFU_gradient(td, method=1, state=1)`` / ``SFD_gradient(td, method=1, state=1)``: spin-flip TDA
+  gradients on a UKS reference with the multicollinear (1) or collinear (2) kernel
+  (xtddft/grad_hb/tduks_sfu.py; ``xtddft_amd/grad.py``)
 
 The arithmetic runs in the HIP library ``_lib/libxtddft_amd.so`` (C ABI in
 ``include/xtddft_amd.h``); there is no CPU fallback.
@@ -25,7 +28,7 @@ from .utils import HA2EV, HA2EV_XSF, order_pyscf2my, so2st, st2so
 __all__ = ["Grid", "MeanField", "Mole", "HA2EV", "HA2EV_XSF", "order_pyscf2my", "so2st", "st2so",
            "XTDA", "SF_TDA", "SF_TDA_up", "SF_TDA_down", "XSF_TDA", "davidson1", "DeviceOperator", "OSsTDA",
            "SI_driver", "si_couple", "states_from_xsf", "states_from_xtda", "states_from_sf_up",
-           "get_soDKH1_somf", "vso_mo"]
+           "get_soDKH1_somf", "vso_mo", "SFU_gradient", "SFD_gradient"]
 
 
 def __getattr__(name):   # lazy: importing the package must not require a GPU
@@ -50,6 +53,9 @@ def __getattr__(name):   # lazy: importing the package must not require a GPU
     if name in ("get_soDKH1_somf", "vso_mo"):
         from . import somf
         return getattr(somf, name)
+    if name in ("SFU_gradient", "SFD_gradient"):
+        from . import grad
+        return getattr(grad, name)
     if name == "DeviceOperator":
         from .operator import DeviceOperator
         return DeviceOperator

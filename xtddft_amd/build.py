@@ -25,7 +25,7 @@ OUT_DIR = os.path.join(HERE, "_lib")
 OBJ_DIR = os.path.join(OUT_DIR, "obj")
 OUT = os.path.join(OUT_DIR, "libxtddft_amd.so")
 SOURCES = ["xt_gemm.hip", "xt_exch.hip", "xt_xcm.hip", "xt_xcw.hip", "xt_xcws.hip", "xt_kernels.hip", "xt_chol.hip", "xt_int.hip", "xt_hint.hip", "xt_grad.hip",
-           "xt_grad_xc.hip", "xt_xc_resp.hip", "xt_tdm.hip", "xt_tdm_sc.hip", "xt_si.hip", "xt_vv10.hip", "xt_stda.hip", "xt_api.hip", "xt_ctx.hip", "xt_ctx_jk.hip",
+           "xt_grad_xc.hip", "xt_xc_resp.hip", "xt_xc_resp_sf.hip", "xt_tdm.hip", "xt_tdm_sc.hip", "xt_si.hip", "xt_vv10.hip", "xt_stda.hip", "xt_api.hip", "xt_ctx.hip", "xt_ctx_jk.hip",
            "xt_ctx_xc.hip"]
 HEADERS = ["xt_internal.h", "xt_hermite.h", "xt_hint_dev.h", "xt_kernels.h", "xt_host.h", "xt_ctx.h", "../../include/xtddft_amd.h"]
 ARCH = os.environ.get("XT_OFFLOAD_ARCH", "gfx950")

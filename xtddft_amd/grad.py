@@ -26,9 +26,17 @@ V^resp through ``xt_xc_resp``) and the XC nuclear-derivative term is
 G_xc[w vxc[rho0]; D0 + T + Z^S] + G_xc[wv[T + Z^S]; D0] (``qc.grad.grad_xc_pairs``), on a grid held
 fixed in space.
 
+The multicollinear kernel (``method = 1``) keeps f1vo and k1ao: with
+omega_xc = sum_g w 2 rho1^T fxc_sf(rho0) rho1, rho1 of the symmetrised transition density X_S, f1vo is
+the potential V_sf of wv1 = 2 w fxc_sf rho1 (``xt_xc_resp_sf``), which stands next to hyb K[X] in the
+coupling matrix, and k1ao the potential of wv2 = w d(2 rho1^T fxc_sf rho1) / d rho0
+(``mcol.sf_mc_kernel_grad``: one backward pass of that scalar, no third-derivative tensor), which
+joins f^xc[T] (``xt_xc_rows``); the XC nuclear-derivative term gains G_xc[wv2; D0] + 2 G_xc[wv1; X_S].
+Its entry is ``SFU_gradient`` / ``SFD_gradient``, the reference's own names; ``nuc_grad_method()`` keeps
+refusing method = 1 and names them.
+
 Refused with NotImplementedError: on a UHF reference method != 0; on a UKS reference method = 0
-(the ALDA0 kernel's density derivative) and method = 1 (third derivatives of the multicollinear
-kernel), a mean field on the host, and everything ``qc.grad.check_ks_gradient_mf`` refuses
+(the ALDA0 kernel's density derivative), a mean field on the host, and everything ``qc.grad.check_ks_gradient_mf`` refuses
 (meta-GGA, range-separated, VV10, ROKS); density fitting, X2C and an ROHF reference on either.
 """
 from __future__ import annotations
@@ -40,8 +48,9 @@ import numpy as np
 from .qc import grad as _g
 
 
-def _scf_of(td):
-    """(the SCF object behind ``td.mf``, whether it is a Kohn-Sham reference) after every refusal."""
+def _scf_of(td, multicollinear=False):
+    """(the SCF object behind ``td.mf``, whether it is a Kohn-Sham reference) after every refusal.
+    ``multicollinear``: the caller is ``SFU_gradient`` / ``SFD_gradient``, which take method = 1."""
     mf = td.mf
     if getattr(mf, "is_rohf", False):
         raise NotImplementedError("spin-flip gradients need a UHF / UKS reference (the reference's "
@@ -67,9 +76,10 @@ def _scf_of(td):
     if td.method == 0:
         raise NotImplementedError("spin-flip gradients with the ALDA0 kernel (method = 0) on a functional: the "
                                   "density derivative of the ALDA0 kernel is not built (method = 2 is)")
-    if td.method == 1:
-        raise NotImplementedError("spin-flip gradients with the multicollinear kernel (method = 1): its third "
-                                  "functional derivatives are not built (method = 2 is)")
+    if td.method == 1 and not multicollinear:
+        raise NotImplementedError("spin-flip gradients with the multicollinear kernel (method = 1) come from "
+                                  "xtddft_amd.grad.SFU_gradient(td) / SFD_gradient(td), the reference's own entry "
+                                  "(grad_hb/tduks_sfu.py); nuc_grad_method() gives the collinear kernel, method = 2")
     return scf, True
 
 
@@ -97,8 +107,13 @@ class KSTerms:
     "b" = flipped-to; the engine keeps alpha, beta, so every density pair is put into the engine's
     order on the way in and every potential back on the way out (``s``)."""
 
-    def __init__(self, scf, s, timings, xc_chunk=None):
+    def __init__(self, scf, s, timings, xc_chunk=None, mc=None):
+        """``mc``: None for the collinear kernel; for the multicollinear one a dict
+        with ``mf`` (the mean field of the TDA object) and ``samples`` (the sample count its roots were
+        computed with)."""
         self.scf, self.s, self.tm = scf, s, timings
+        self.mc = mc
+        self.x_s = self.wv1 = self.wv2 = None      # multicollinear: X_S, wv1 (4, G), wv2 (2, 4, G) alpha, beta
         self.eng = scf.device_engine
         if self.eng is None:
             raise RuntimeError("the XC terms run on the GPU: run the SCF after mf.to_device()")
@@ -122,6 +137,44 @@ class KSTerms:
         """V^resp (2, nao, nao) of a symmetric density pair, in the labels of ``grad_elec``."""
         return self._order(self._timed(self.eng.fxc_response, self._order(dm), want=("v",))["v"])
 
+    def sf_coupling(self, x_s):
+        """V_sf (nao, nao), the potential of wv1 = 2 w fxc_sf rho1[X_S], which stands next to hyb K[X] in
+        the coupling matrix; None with the collinear kernel.  Keeps wv1 and wv2 = w d(2 rho1^T fxc_sf
+        rho1) / d rho0 (``mcol.sf_mc_kernel_grad``) for ``vxc_resp_t`` and ``grad``."""
+        if self.mc is None:
+            return None
+        import torch
+        from .mcol import sf_mc_kernel, sf_mc_kernel_grad
+        eng, mf, ns = self.eng, self.mc["mf"], self.mc["samples"]
+        kern = sf_mc_kernel(mf, ns, device=eng.dev.index)
+        t0 = time.perf_counter()
+        out = eng.fxc_sf_response(x_s, kern, want=("v", "wv", "rho1"))
+        torch.cuda.synchronize(eng.dev)
+        self.tm["xc_sf_response_s"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        nk = 4 if eng.xctype == "GGA" else 1
+        # rho0 through the engine's own GEMM (a fixed summation order): equal calls give equal bits
+        with torch.cuda.device(eng.dev):
+            rho0 = eng.rho(np.asarray([c[:, o > 0] @ c[:, o > 0].T for c, o in zip(self.scf.mo_coeff, self.scf.mo_occ)]))
+        _, dq = sf_mc_kernel_grad(mf, out["rho1"][:nk], ns, device=eng.dev.index, rho=rho0)
+        wv2 = torch.zeros((2, 4, out["wv"].shape[1]), dtype=torch.float64, device=eng.dev)
+        wv2[:, :nk] = torch.as_tensor(dq, device=eng.dev) * eng.w
+        torch.cuda.synchronize(eng.dev)
+        self.tm["mc_kernel_grad_s"] = time.perf_counter() - t0
+        self.x_s, self.wv1, self.wv2 = np.asarray(x_s), out["wv"], wv2
+        return out["v"]
+
+    def vxc_resp_t(self, dm):
+        """What joins ``veff0doo``: f^xc[T], and with the multicollinear kernel V^k, the potential of
+        wv2, from the same row pass (potentials are linear in their weights)."""
+        if self.mc is None:
+            return self.vxc_resp(dm)
+        wv = self._timed(self.eng.fxc_response, self._order(dm), want=("wv",))["wv"]
+        t0 = time.perf_counter()
+        v = self.eng.rows_potential(wv + self.wv2)
+        self.tm["xc_sf_response_s"] += time.perf_counter() - t0
+        return self._order(v)
+
     def vresp(self, dm):
         """J[dm_a + dm_b] - hyb K[dm_s] + V^resp_s[dm]: what the Z-vector equations apply."""
         t0 = time.perf_counter()
@@ -132,7 +185,8 @@ class KSTerms:
 
     def grad(self, d0, tz):
         """G_xc[w vxc[rho0]; D0 + T + Z^S] + G_xc[wv[T + Z^S]; D0], (natm, 3); d0, tz in the labels of
-        ``grad_elec``."""
+        ``grad_elec``.  With the multicollinear kernel wv2 joins wv[T + Z^S] and 2 G_xc[wv1; X_S] is
+        added: a one-channel term, run as a two-spin pair whose second channel is zero."""
         import torch
         from .qc import xc as _xc
         eng = self.eng
@@ -142,7 +196,12 @@ class KSTerms:
         with torch.cuda.device(eng.dev):
             h0 = _xc.eval_xc_eff_torch(self.scf.xc, eng.rho(d0), deriv=1)[1] * eng.w
         st = {}
-        de = _g.grad_xc_pairs(self.scf, [(h0, d0 + tz), (wv, d0)], chunk=self.xc_chunk, stats=st)
+        pairs = [(h0, d0 + tz), (wv, d0)]
+        if self.mc is not None:
+            h1 = torch.zeros_like(self.wv2)
+            h1[0] = 2.0 * self.wv1
+            pairs = [(h0, d0 + tz), (wv + self.wv2, d0), (h1, np.asarray([self.x_s, np.zeros_like(self.x_s)]))]
+        de = _g.grad_xc_pairs(self.scf, pairs, chunk=self.xc_chunk, stats=st)
         self.tm["grad_xc_s"] = time.perf_counter() - t0
         self.tm["grad_xc_stats"] = st
         self.de_xc = de
@@ -183,11 +242,15 @@ def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, 
     dmxab = orbvb @ x_ab @ orboa.T
     dmSx, dmAx = (dmxab + dmxab.T) / 2, (dmxab - dmxab.T) / 2
     vj, vk = get_jk((dmta, dmtb, dmSx, dmAx))                     # vk carries hyb from here on
-    vkmo = mo_coeff[1].T @ (vk[2] + vk[3]) @ mo_coeff[0]          # K[X_S] + K[X_A]: beta rows, alpha columns
+    kx = vk[2] + vk[3]                                            # K[X_S] + K[X_A]
+    vsf = None if xc is None else xc.sf_coupling(dmSx)            # multicollinear kernel: hyb K[X] - V_sf
+    if vsf is not None:
+        kx = kx - vsf
+    vkmo = mo_coeff[1].T @ kx @ mo_coeff[0]                       # beta rows, alpha columns
     veff0dooa = vj[0] + vj[1] - vk[0]
     veff0doob = vj[0] + vj[1] - vk[1]
-    if xc is not None:           # f^xc[T]
-        fxt = xc.vxc_resp(((dmta + dmta.T) * 0.5, (dmtb + dmtb.T) * 0.5))
+    if xc is not None:           # f^xc[T] (+ V^k)
+        fxt = xc.vxc_resp_t(((dmta + dmta.T) * 0.5, (dmtb + dmtb.T) * 0.5))
         veff0dooa, veff0doob = veff0dooa + fxt[0], veff0doob + fxt[1]
     # right-hand side of the Z-vector equations
     wvoa = 2.0 * (orbva.T @ veff0dooa @ orboa + fockamo[nocca:, :nocca] @ ta.T - vkmo[noccb:, nocca:].T @ x_ab)
@@ -268,9 +331,16 @@ class SFGradients:
     cphf_max_cycle = 500
     cphf_conv_tol = 1e-10
 
+    _multicollinear = False      # SFU_gradient / SFD_gradient: method = 1 is accepted
+
     def __init__(self, td):
         self.base = td
-        self._scf, self.is_ks = _scf_of(td)
+        self._scf, self.is_ks = _scf_of(td, self._multicollinear)
+        # the multicollinear kernel is differentiated at the sample count the roots were computed with
+        self.collinear_samples = None
+        if td.method == 1:
+            from .sf_tda import DAVIDSON_SAMPLES, EXPLICIT_SAMPLES
+            self.collinear_samples = int(td.collinear_samples or (DAVIDSON_SAMPLES if td.davidson else EXPLICIT_SAMPLES))
         self.mol = self._scf.mol
         self.state = 1
         self.atmlst = None
@@ -298,7 +368,8 @@ class SFGradients:
         flip = td.isf == 1
         if self.is_ks:
             self.timings.clear()
-            xc = KSTerms(self._scf, (1, 0) if flip else (0, 1), self.timings, self.xc_chunk)
+            mc = dict(mf=td.mf, samples=self.collinear_samples) if td.method == 1 else None
+            xc = KSTerms(self._scf, (1, 0) if flip else (0, 1), self.timings, self.xc_chunk, mc=mc)
             de = grad_elec(self._scf, sf_amplitude(td, self.state - 1), flip, dev, self.cphf_conv_tol,
                            self.cphf_max_cycle, self.timings, hyb=float(self._scf.hyb), xc=xc)
             self.de_xc = xc.de_xc
@@ -316,3 +387,52 @@ class SFGradients:
             self.atmlst = atmlst
         self.de = self.grad_elec(atmlst) + self.grad_nuc(atmlst=atmlst)
         return self.de
+
+
+class _SFKernelGradient(SFGradients):
+    """``SFU_gradient`` / ``SFD_gradient``: the reference's entry to the spin-flip TDA gradient on a UKS
+    reference (grad_hb/tduks_sfu.py ``SFU_gradient(td, method=1, state=1)``), which names the kernel."""
+
+    _multicollinear = True
+    _td_class = None
+
+    def __init__(self, td, method=1, state=1):
+        from . import sf_tda
+        want = getattr(sf_tda, self._td_class)
+        if not isinstance(td, want):
+            raise TypeError(f"{type(self).__name__} takes an {self._td_class} object, not {type(td).__name__}")
+        if method != td.method:
+            raise ValueError(f"{type(self).__name__}: method = {method}, but the roots were computed with "
+                             f"method = {td.method}")
+        if method == 0:
+            raise NotImplementedError("spin-flip gradients with the ALDA0 kernel (method = 0) are not built "
+                                      "(grad_hb/tduks_sfu.py raises likewise); methods 1 and 2 are")
+        super().__init__(td)
+        self.method = method
+        self.state = state
+
+    def kernel(self, atmlst=None):
+        return super().kernel(None, atmlst)
+
+
+class SFU_gradient(_SFKernelGradient):
+    """Gradient of a spin-flip-up TDA state on a UKS reference (LDA / GGA, pure or global hybrid, on a
+    device): ``SFU_gradient(td, method=1, state=1).kernel()`` with ``td`` an ``SF_TDA_up`` whose
+    ``kernel()`` has run and ``method`` equal to ``td.method``.  method = 1 is the multicollinear kernel
+    (DESIGN section 18), method = 2 runs exactly what ``td.nuc_grad_method()`` runs, method = 0 is not
+    built.  The multicollinear kernel is differentiated at the sample count the roots were computed
+    with (``collinear_samples``), not at the reference's fixed 20: only then is the result the
+    derivative of the printed energy.
+
+    Why two entries: ``nuc_grad_method()`` is pinned to refuse method = 1 (and stays the entry for
+    Hartree-Fock references and the collinear kernel); the multicollinear gradient comes in under the
+    name the reference gives it.  Attributes as ``SFGradients``; ``timings`` gains ``mc_kernel_grad_s``
+    (the autograd pass of ``mcol.sf_mc_kernel_grad``) and ``xc_sf_response_s`` (``xt_xc_resp_sf`` /
+    ``xt_xc_rows`` with their GEMMs)."""
+    _td_class = "SF_TDA_up"
+
+
+class SFD_gradient(_SFKernelGradient):
+    """``SFU_gradient`` for a spin-flip-down state (``td`` an ``SF_TDA_down``): the same derivation with
+    the spin labels exchanged.  The reference's ``SFD_gradient`` is an empty stub; this one works."""
+    _td_class = "SF_TDA_down"

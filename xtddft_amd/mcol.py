@@ -114,3 +114,68 @@ def sf_mc_kernel(mf, collinear_samples: int = 60, device=None, max_points: int =
         mf.extra[key] = res
         mf.extra[key + ("orbitals",)] = ident
     return res
+
+
+def sf_mc_kernel_grad(mf, rho1, collinear_samples: int = 60, device=None, max_points: int = 1 << 20, rho=None):
+    """The density derivative of the multicollinear kernel along a fixed transition density, without
+    the third-derivative tensor: with fxc_sf = ``sf_mc_kernel(...)`` and ``rho1`` (nk, ngrid),
+
+        q(g)          = 2 rho1(:, g)^T fxc_sf(rho0)(:, :, g) rho1(:, g)
+        dq(s, k, g)   = d q(g) / d rho0_s(k, g)          with rho1 held fixed
+
+    Returns (q (ngrid,), dq (2, nk, ngrid)), un-weighted like the kernel itself; the gradient's weights
+    are wv2 = w dq.  rho1^T (d2 eps / ds ds) rho1 at a sample is the second derivative of eps along the
+    direction (rho_a, rho_b) += (rho1, -rho1) / 2, so q is two directional derivatives of the energy
+    density (``qc.xc.energy_density_torch``) summed over the Gauss-Legendre samples, and dq is one
+    backward pass of that scalar.  RHO_SHIFT, the sample nodes, the batching over grid points x samples,
+    the density screening and the exchange flags are those of ``sf_mc_kernel``: q equals
+    ``2 einsum('xg,xyg,yg->g', rho1, sf_mc_kernel(...), rho1)`` to round-off, and a point the kernel
+    screens out has dq = 0 exactly.  ``rho`` (2, nk, ngrid): the spin densities, default the SCF density
+    of ``mf``.  Host arrays in, host arrays out; device tensors when the grid's AO values live in HBM."""
+    import torch
+    from .qc import xc as _xc
+    if mf.xctype not in ("LDA", "GGA"):
+        raise NotImplementedError(f"sf_mc_kernel_grad covers LDA / GGA functionals, not {mf.xctype}")
+    dev = _torch_device(mf, device)
+    rho = ground_state_rho(mf, dev) if rho is None else torch.as_tensor(rho, dtype=torch.float64, device=dev)
+    r1 = torch.as_tensor(rho1, dtype=torch.float64, device=dev)
+    nk, ng = rho.shape[1], rho.shape[2]
+    if r1.shape != (nk, ng):
+        raise ValueError(f"sf_mc_kernel_grad: rho1 of shape {tuple(r1.shape)}, expected {(nk, ng)}")
+    t, w = np.polynomial.legendre.leggauss(int(collinear_samples))
+    t, w = 0.5 * t + 0.5, 0.5 * w
+    q = torch.zeros(ng, dtype=torch.float64, device=dev)
+    dq = torch.zeros((2, nk, ng), dtype=torch.float64, device=dev)
+    gb = max(1, min(ng, max_points))                       # grid points per batch
+    sb = max(1, min(len(t), max_points // gb))              # samples per batch
+    for g0 in range(0, ng, gb):
+        g1 = min(ng, g0 + gb)
+        r0 = rho[:, :, g0:g1].detach().clone().requires_grad_(True)
+        tt = r0[0] + r0[1] + RHO_SHIFT
+        ss = r0[0] - r0[1] + RHO_SHIFT
+        half = 0.5 * r1[:, g0:g1]
+        for k0 in range(0, len(t), sb):
+            k1 = min(len(t), k0 + sb)
+            ns = k1 - k0
+            tk = torch.as_tensor(t[k0:k1], dtype=torch.float64, device=dev)
+            wk = torch.as_tensor(w[k0:k1], dtype=torch.float64, device=dev)
+            sk = ss[:, None, :] * tk[None, :, None]                                   # (nk, ns, g)
+            ud = torch.stack([0.5 * (tt[:, None, :] + sk), 0.5 * (tt[:, None, :] - sk)]).reshape(2, nk, -1)
+            idx = torch.nonzero((ud[0, 0] + ud[1, 0]).detach() > _xc.DENS_THRESHOLD).squeeze(1)
+            if idx.numel() == 0:
+                continue
+            x = ud[:, :, idx]
+            dirn = torch.stack([half, -half])[:, :, None, :].expand(2, nk, ns, g1 - g0).reshape(2, nk, -1)[:, :, idx]
+            eps = _xc.energy_density_torch(mf.xc, x)
+            if not torch.is_tensor(eps) or not eps.requires_grad:
+                continue
+            d1 = (torch.autograd.grad(eps.sum(), x, create_graph=True)[0] * dirn).sum((0, 1))
+            d2 = (torch.autograd.grad(d1.sum(), x, create_graph=True)[0] * dirn).sum((0, 1))
+            full = torch.zeros(ns * (g1 - g0), dtype=torch.float64, device=dev).index_add(0, idx, d2)
+            qb = 2.0 * (full.reshape(ns, g1 - g0) * wk[:, None]).sum(0)
+            dq[:, :, g0:g1] += torch.autograd.grad(qb.sum(), r0, retain_graph=k1 < len(t))[0]
+            q[g0:g1] += qb.detach()
+    ao = mf.grids.ao
+    if isinstance(ao, torch.Tensor) and ao.is_cuda:
+        return q, dq
+    return q.cpu().numpy(), dq.cpu().numpy()

@@ -303,6 +303,132 @@ class DeviceEngine:
             out["wv"] = wv
         return out
 
+    # ------------------------------------------------------------ spin-flip channel, given weights
+    def _xc_chunk(self):
+        from .grad import default_xc_chunk
+        ng = int(self.w.shape[0])
+        chunk = default_xc_chunk(self.n, ng) if self.fxc_chunk is None else int(self.fxc_chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        return ng, chunk
+
+    def fxc_sf_response(self, x_s, fxc_sf, want=("v", "wv", "rho1"), stats=None):
+        """The spin-flip channel of the multicollinear kernel applied to the symmetric transition
+        density ``x_s`` (nao, nao): per grid chunk the GEMM c = phi X_S, one ``xt_xc_resp_sf`` call
+        (rho1, wv = 2 w fxc_sf rho1 and b, csrc/xt_xc_resp_sf.hip) and the GEMM phi^T b.  ``fxc_sf``
+        (nk, nk, G): ``mcol.sf_mc_kernel``.  ``want``: "v" -- V_sf (nao, nao), a host array, phi^T b plus
+        its transpose for GGA; "wv" -- the unhalved weights (4, G) on the device, planes 1..3 zero for
+        LDA; "rho1" -- (4, G) on the device likewise.  Returns a dict; ``stats`` as ``fxc_response``."""
+        import time
+        torch = self.torch
+        if self.xctype not in ("LDA", "GGA"):
+            raise NotImplementedError(f"the AO-route XC response covers LDA / GGA functionals, not {self.xctype}")
+        unknown = set(want) - {"v", "wv", "rho1"}
+        if unknown or not want:
+            raise ValueError(f"fxc_sf_response: want is any of 'v', 'wv', 'rho1', got {tuple(want)}")
+        gga = self.xctype == "GGA"
+        nk = 4 if gga else 1
+        n, ao = self.n, self.ao
+        ng, chunk = self._xc_chunk()
+        kw = dict(dtype=torch.float64, device=self.dev)
+        f = torch.as_tensor(fxc_sf, **kw).contiguous()
+        if f.shape != (nk, nk, ng):
+            raise ValueError(f"fxc_sf_response: kernel of shape {tuple(f.shape)}, expected {(nk, nk, ng)}")
+        d = torch.as_tensor(np.ascontiguousarray(np.asarray(x_s, dtype=np.float64)), device=self.dev)
+        if d.shape != (n, n):
+            raise ValueError(f"fxc_sf_response: density of shape {tuple(d.shape)}, expected {(n, n)}")
+        need_v, need_wv, need_r = "v" in want, "wv" in want, "rho1" in want
+        wv = torch.zeros((4, ng), **kw) if need_wv else None
+        r1 = torch.zeros((4, ng), **kw) if need_r else None
+        v = torch.zeros((n, n), **kw) if need_v else None
+        tg = tk = 0.0
+        with torch.cuda.device(self.dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+            for g0 in range(0, ng, chunk):
+                g1 = min(ng, g0 + chunk)
+                m = g1 - g0
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    t0 = time.perf_counter()
+                a0 = ao[0, g0:g1]
+                c = torch.empty((m, n), **kw)
+                self._gemm(0, 0, m, n, n, 1.0, a0, n, d, n, 0.0, c, n)                   # c = phi X_S
+                b = torch.empty((m, n), **kw) if need_v else None
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    tg += time.perf_counter() - t0
+                    t0 = time.perf_counter()
+                _capi.check(self.L.xt_xc_resp_sf(m, n, _capi.XC[self.xctype], a0.data_ptr(), ao.stride(0), n,
+                                                 c.data_ptr(), n, f[..., g0:].data_ptr(), ng, self.w[g0:].data_ptr(),
+                                                 r1[:, g0:].data_ptr() if need_r else None,
+                                                 wv[:, g0:].data_ptr() if need_wv else None, ng,
+                                                 b.data_ptr() if need_v else None, n, st), "xt_xc_resp_sf")
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    tk += time.perf_counter() - t0
+                    t0 = time.perf_counter()
+                if need_v:
+                    self._gemm(1, 0, n, n, m, 1.0, a0, n, b, n, 1.0, v, n)               # v += phi^T b
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    tg += time.perf_counter() - t0
+        if stats is not None:
+            stats.update(gemm_s=tg, xc_resp_sf_s=tk, chunk=chunk, ngrid=ng, chunks=(ng + chunk - 1) // chunk)
+        out = {}
+        if need_v:
+            out["v"] = (v + v.T if gga else v).cpu().numpy()
+        if need_wv:
+            out["wv"] = wv
+        if need_r:
+            out["rho1"] = r1
+        return out
+
+    def rows_potential(self, wv, stats=None):
+        """The potentials of given grid weights ``wv`` (nch, 4, G) on the device ("eff" layout, nothing
+        halved, LDA reads plane 0), nch = 1..4 channels: per grid chunk one ``xt_xc_rows`` call, which
+        reads the AO rows once for all channels, and one GEMM phi^T b_ch per channel.  Returns
+        (nch, nao, nao), a host array, with the transpose added for GGA (the conventions of ``vxc``)."""
+        import time
+        torch = self.torch
+        if self.xctype not in ("LDA", "GGA"):
+            raise NotImplementedError(f"the AO-route XC response covers LDA / GGA functionals, not {self.xctype}")
+        gga = self.xctype == "GGA"
+        n, ao = self.n, self.ao
+        ng, chunk = self._xc_chunk()
+        kw = dict(dtype=torch.float64, device=self.dev)
+        wv = torch.as_tensor(wv, **kw).contiguous()
+        if wv.dim() != 3 or not 1 <= wv.shape[0] <= 4 or wv.shape[1:] != (4, ng):
+            raise ValueError(f"rows_potential: weights of shape {tuple(wv.shape)}, expected (1..4, 4, {ng})")
+        nch = int(wv.shape[0])
+        v = torch.zeros((nch, n, n), **kw)
+        tg = tk = 0.0
+        with torch.cuda.device(self.dev):
+            st = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+            for g0 in range(0, ng, chunk):
+                g1 = min(ng, g0 + chunk)
+                m = g1 - g0
+                a0 = ao[0, g0:g1]
+                b = torch.empty((nch, m, n), **kw)
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    t0 = time.perf_counter()
+                _capi.check(self.L.xt_xc_rows(m, n, _capi.XC[self.xctype], nch, a0.data_ptr(), ao.stride(0), n,
+                                              wv[..., g0:].data_ptr(), ng, b.data_ptr(), n, st), "xt_xc_rows")
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    tk += time.perf_counter() - t0
+                    t0 = time.perf_counter()
+                for ch in range(nch):
+                    self._gemm(1, 0, n, n, m, 1.0, a0, n, b[ch], n, 1.0, v[ch], n)       # v_ch += phi^T b_ch
+                if stats is not None:
+                    torch.cuda.synchronize(self.dev)
+                    tg += time.perf_counter() - t0
+        if stats is not None:
+            stats.update(gemm_s=tg, xc_rows_s=tk, chunk=chunk, ngrid=ng, chunks=(ng + chunk - 1) // chunk)
+        if gga:
+            v = v + v.transpose(1, 2)
+        return v.cpu().numpy()
+
     def kernels(self, dms):
         """(fxc (2, ncomp, 2, ncomp, G), ALDA0 fxc_ab (G)) at the SCF density:
         cache_xc_kernel (XTDA.py:504) and cache_xc_kernel_sf (SF_TDA.py:69-85)."""

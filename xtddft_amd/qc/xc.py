@@ -577,3 +577,27 @@ def eval_xc_eff_torch(xc: str, rho, deriv: int = 1):
     if xctype == "MGGA":
         _screen_spin(rho, vxc, fxc, torch)
     return exc, vxc, fxc
+
+
+def energy_density_torch(xc: str, x):
+    """The differentiable core of ``eval_xc_eff_torch``: the energy density eps (n,) of an LDA / GGA
+    functional at spin densities ``x`` (2, ncomp, n), a torch tensor that may carry a graph (nothing is
+    detached, so derivatives of any order with respect to what ``x`` was built from are available).  The
+    same clamps and per-channel exchange flags as ``eval_xc_eff_torch``; the caller selects the points
+    above DENS_THRESHOLD, as that function does."""
+    import torch
+    comps, _, xctype = parse_xc(xc)
+    ncomp = NCOMP[xctype]
+    if xctype not in ("LDA", "GGA"):
+        raise NotImplementedError(f"energy_density_torch covers LDA / GGA functionals, not {xctype}")
+    rs = x[:, :ncomp]
+    ra = torch.clamp(rs[0, 0], min=1e-30)
+    rb = torch.clamp(rs[1, 0], min=1e-30)
+    if ncomp >= 4:
+        ga, gb = rs[0, 1:4], rs[1, 1:4]
+        saa, sab, sbb = (ga * ga).sum(0), (ga * gb).sum(0), (gb * gb).sum(0)
+    else:
+        saa = sab = sbb = torch.zeros_like(ra)
+    on = ((rs[0, 0] > DENS_THRESHOLD).to(torch.float64).detach(),
+          (rs[1, 0] > DENS_THRESHOLD).to(torch.float64).detach())
+    return _energy_density(comps, ra, rb, saa, sab, sbb, None, None, torch, on)

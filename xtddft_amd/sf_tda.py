@@ -198,7 +198,8 @@ class _SFBase:
         Hartree-Fock reference with method 0; on a UKS reference (LDA / GGA, pure or global hybrid,
         after ``to_device()``) with the collinear kernel, method 2.  Methods 0 and 1 on a functional,
         a KS mean field on the host and what ``qc.grad.check_ks_gradient_mf`` refuses raise
-        NotImplementedError."""
+        NotImplementedError; the multicollinear kernel, method 1, has its own entry under the
+        reference's names, ``xtddft_amd.grad.SFU_gradient(td)`` / ``SFD_gradient(td)``."""
         from .grad import SFGradients
         return SFGradients(self)
 
