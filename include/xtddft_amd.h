@@ -567,6 +567,22 @@ int xt_grad_jk(int nbra, const int* bra_info, const double* bra_prim, const doub
                int lbra, int lket, int nterm, const double* wj, const double* wk, const double* p,
                const double* q, long nao, int strip, int natm, double* work, long nwork, double* out,
                void* hip_stream);
+/* xt_grad_jk with a Coulomb list and an exchange list of their own,
+     Gamma_abcd = sum_{t < nj} wj[t] PJ_t[a,b] QJ_t[c,d] + sum_{t < nk} wk[t] PK_t[a,c] QK_t[b,d],
+   for two-particle densities of more than eight pairs whose pairs are Coulomb-only or exchange-only
+   (the U-TDA gradient on a hybrid: three Coulomb and eight exchange pairs): one pass over the
+   derivative integrals, and one product per pair where xt_grad_jk forms two.  The integral code, the
+   (d, c) image, the Gamma cache, the strips and the two-stage reduction are xt_grad_jk's own (one
+   kernel body, instantiated for either Gamma); tables, strip, work / nwork, out, lbra / lket as there.
+     wj, pj, qj    nj host weights; device, nj matrices nao x nao each (as p, q of xt_grad_jk)
+     wk, pk, qk    nk host weights; device, nk matrices each
+   0 <= nj <= 8, 0 <= nk <= 8, nj + nk >= 1.  A list whose count is zero is not read: its three
+   pointers may be null.  Equal inputs give equal bits. */
+int xt_grad_jk2(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao,
+                int nket, const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao,
+                int lbra, int lket, int nj, const double* wj, const double* pj, const double* qj, int nk,
+                const double* wk, const double* pk, const double* qk, long nao, int strip, int natm,
+                double* work, long nwork, double* out, void* hip_stream);
 /* AO values (deriv 0) or values and gradients (deriv 1) of normalised spherical
    AOs on grid points (PySCF mol.eval_ao / ni.block_loop, SF_TDA.py:63-68, the AO
    input of cache_xc_kernel / nr_uks_fxc, XTDA.py:504,514), device pointers:

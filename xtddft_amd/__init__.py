@@ -18,6 +18,8 @@ Reference-compatible entry points (PySCF-style operator API):
 * ``SFU_gradient(td, method=1, state=1)`` / ``SFD_gradient(td, method=1, state=1)``: spin-flip TDA
   gradients on a UKS reference with the multicollinear (1) or collinear (2) kernel
   (xtddft/grad_hb/tduks_sfu.py; ``xtddft_amd/grad.py``)
+* ``XTDA(mol, mf).nuc_grad_method()``: U-TDA gradients on a UHF / UKS reference, LDA / GGA, pure and
+  global hybrid (xtddft/grad_jp/grad/utdhf.py with Y = 0; ``xtddft_amd/grad_utda.py``)
 
 The arithmetic runs in the HIP library ``_lib/libxtddft_amd.so`` (C ABI in
 ``include/xtddft_amd.h``); there is no CPU fallback.

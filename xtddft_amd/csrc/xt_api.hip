@@ -206,6 +206,32 @@ extern "C" int xt_grad_jk(int nbra, const int* bra_info, const double* bra_prim,
   return r ? fail(r, "grad_jk launch failed") : 0;
 }
 
+extern "C" int xt_grad_jk2(int nbra, const int* bra_info, const double* bra_prim, const double* eb,
+                           const int* bra_ao, int nket, const int* ket_info, const double* ket_prim,
+                           const double* ek, const int* ket_ao, int lbra, int lket, int nj, const double* wj,
+                           const double* pj, const double* qj, int nk, const double* wk, const double* pk,
+                           const double* qk, long nao, int strip, int natm, double* work, long nwork, double* out,
+                           void* stream) {
+  if (nbra < 0 || nket < 0 || nao < 0 || natm < 0 || nwork < 0) return fail(XT_ERR_ARG, "xt_grad_jk2: negative size");
+  if (strip < 1) return fail(XT_ERR_ARG, "xt_grad_jk2: strip must be at least 1");
+  if (lbra < 0 || lket < 0 || lbra > kHintMaxLBra || lbra + lket > kHintMaxL)
+    return fail(XT_ERR_ARG, "xt_grad_jk2: bra order <= 8 and total order <= 14");
+  if (nj < 0 || nj > kGradMaxTerms) return fail(XT_ERR_ARG, "xt_grad_jk2: nj must be 0..8");
+  if (nk < 0 || nk > kGradMaxTerms) return fail(XT_ERR_ARG, "xt_grad_jk2: nk must be 0..8");
+  if (nj + nk < 1) return fail(XT_ERR_ARG, "xt_grad_jk2: nj and nk are both zero");
+  if (nj > 0 && !wj) return fail(XT_ERR_ARG, "xt_grad_jk2: null wj with nj > 0");
+  if (nk > 0 && !wk) return fail(XT_ERR_ARG, "xt_grad_jk2: null wk with nk > 0");
+  if (nbra == 0 || nket == 0 || natm == 0) return 0;   // nothing to add
+  if (nj > 0 && (!pj || !qj)) return fail(XT_ERR_ARG, "xt_grad_jk2: null pj or qj with nj > 0");
+  if (nk > 0 && (!pk || !qk)) return fail(XT_ERR_ARG, "xt_grad_jk2: null pk or qk with nk > 0");
+  if (!bra_info || !bra_prim || !eb || !bra_ao || !ket_info || !ket_prim || !ek || !ket_ao || !work || !out)
+    return fail(XT_ERR_ARG, "xt_grad_jk2: null table, workspace or output");
+  if (nwork < grad_jk_work(nbra, nket, strip)) return fail(XT_ERR_ARG, "xt_grad_jk2: workspace too small");
+  const int r = grad_jk2(nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra, lket, nj, wj,
+                         pj, qj, nk, wk, pk, qk, nao, strip, natm, work, out, (hipStream_t)stream);
+  return r ? fail(r, "grad_jk2 launch failed") : 0;
+}
+
 extern "C" int xt_eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info,
                           const double* shell_data, const double* sph, const double* ao_norm, int deriv,
                           double* out, long ldo, long comp_stride, void* stream) {

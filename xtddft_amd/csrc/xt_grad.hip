@@ -4,7 +4,10 @@
 // libcint's int2e_ip1):
 //
 //   g[A][m] = sum_{a in A} sum_{b,c,d} (d_m a  b | c d) Gamma_abcd,      m = x, y, z
-//   Gamma_abcd = sum_{t < nterm} wj[t] P_t[a,b] Q_t[c,d] + wk[t] P_t[a,c] Q_t[b,d]
+//   Gamma_abcd = sum_{t < nterm} wj[t] P_t[a,b] Q_t[c,d] + wk[t] P_t[a,c] Q_t[b,d]           (xt_grad_jk)
+//   Gamma_abcd = sum_{t < nj} wj[t] PJ_t[a,b] QJ_t[c,d] + sum_{t < nk} wk[t] PK_t[a,c] QK_t[b,d]   (xt_grad_jk2)
+//
+// One kernel body serves both: k_grad_jk is a template over the functor that forms Gamma.
 //
 // d_m a is what the bra table holds (qc/ints.py deriv_tables: the derivative with respect to the
 // centre of a, the negative of the electron-coordinate derivative; the host fixes the sign);
@@ -41,27 +44,48 @@ struct GradTerms {
 // (every s / p quartet: 9 x 9); larger blocks recompute the element per primitive quartet
 constexpr int kGradCache = 81;
 
-__device__ __forceinline__ double grad_gamma(const GradTerms& tm, const double* __restrict__ P,
-                                             const double* __restrict__ Q, long n, long ia, long ib, long ic,
-                                             long id) {
-  double g = 0.0;
-  const long n2 = n * n;
-  for (int t = 0; t < tm.nterm; ++t) {
-    const double* p = P + t * n2;
-    const double* q = Q + t * n2;
-    g += tm.wj[t] * p[ia * n + ib] * q[ic * n + id] + tm.wk[t] * p[ia * n + ic] * q[ib * n + id];
+// How Gamma_abcd is formed: k_grad_jk is a template over one of these.  GammaPairs is xt_grad_jk's
+// (every pair carries a Coulomb and an exchange weight), GammaLists xt_grad_jk2's (a Coulomb list
+// and an exchange list of their own, so that a pair costs one product, not two).
+struct GammaPairs {
+  GradTerms tm;
+  const double* __restrict__ P;
+  const double* __restrict__ Q;
+  __device__ __forceinline__ double operator()(long n, long ia, long ib, long ic, long id) const {
+    double g = 0.0;
+    const long n2 = n * n;
+    for (int t = 0; t < tm.nterm; ++t) {
+      const double* p = P + t * n2;
+      const double* q = Q + t * n2;
+      g += tm.wj[t] * p[ia * n + ib] * q[ic * n + id] + tm.wk[t] * p[ia * n + ic] * q[ib * n + id];
+    }
+    return g;
   }
-  return g;
-}
+};
+
+struct GammaLists {
+  int nj, nk;
+  double wj[kGradMaxTerms], wk[kGradMaxTerms];
+  const double* __restrict__ PJ;
+  const double* __restrict__ QJ;
+  const double* __restrict__ PK;
+  const double* __restrict__ QK;
+  __device__ __forceinline__ double operator()(long n, long ia, long ib, long ic, long id) const {
+    double g = 0.0;
+    const long n2 = n * n;
+    for (int t = 0; t < nj; ++t) g += wj[t] * PJ[t * n2 + ia * n + ib] * QJ[t * n2 + ic * n + id];
+    for (int t = 0; t < nk; ++t) g += wk[t] * PK[t * n2 + ia * n + ic] * QK[t * n2 + ib * n + id];
+    return g;
+  }
+};
 
 // MAXL: largest total order, MAXLB: largest bra order (they size R / S and M)
-template <int MAXL, int MAXLB>
+template <int MAXL, int MAXLB, class Gamma>
 __global__ void __launch_bounds__(64)
 k_grad_jk(int nbra, const int* __restrict__ bra_info, const double* __restrict__ bra_prim,
           const double* __restrict__ eb, const int* __restrict__ bra_ao, int nket,
           const int* __restrict__ ket_info, const double* __restrict__ ket_prim, const double* __restrict__ ek,
-          const int* __restrict__ ket_ao, GradTerms tm, const double* __restrict__ P,
-          const double* __restrict__ Q, long nao, int nstrip, double* __restrict__ partial) {
+          const int* __restrict__ ket_ao, Gamma gm, long nao, int nstrip, double* __restrict__ partial) {
   const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= (long)nbra * nstrip) return;
   const int s = (int)(id / nbra), k = (int)(id % nbra);
@@ -84,8 +108,8 @@ k_grad_jk(int nbra, const int* __restrict__ bra_info, const double* __restrict__
         const long ic = c0 + c / ncd, idd = d0 + c % ncd;
         for (int ab = 0; ab < nab; ++ab) {
           const long ia = a0 + ab / ncb, ib = b0 + ab % ncb;
-          double v = grad_gamma(tm, P, Q, nao, ia, ib, ic, idd);
-          if (image) v += grad_gamma(tm, P, Q, nao, ia, ib, idd, ic);
+          double v = gm(nao, ia, ib, ic, idd);
+          if (image) v += gm(nao, ia, ib, idd, ic);
           G[c * nab + ab] = v;
         }
       }
@@ -121,8 +145,8 @@ k_grad_jk(int nbra, const int* __restrict__ bra_info, const double* __restrict__
               gam = G[c * nab + ab];
             } else {
               const long ia = a0 + ab / ncb, ib = b0 + ab % ncb;
-              gam = grad_gamma(tm, P, Q, nao, ia, ib, ic, idd);
-              if (image) gam += grad_gamma(tm, P, Q, nao, ia, ib, idd, ic);
+              gam = gm(nao, ia, ib, ic, idd);
+              if (image) gam += gm(nao, ia, ib, idd, ic);
             }
             gam *= pref;
             for (int m = 0; m < 3; ++m) {
@@ -167,27 +191,22 @@ long grad_jk_work(int nbra, int nket, int strip) {
   return 3 * (long)nbra * (nstrip + 1);
 }
 
-int grad_jk(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao, int nket,
-            const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao, int lbra, int lket,
-            int nterm, const double* wj, const double* wk, const double* P, const double* Q, long nao, int strip,
-            int natm, double* work, double* out, hipStream_t st) {
-  if (nbra == 0 || nket == 0 || natm == 0) return 0;
+// the three launches of one call, for either way of forming Gamma
+template <class Gamma>
+static int grad_launch(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao,
+                       int nket, const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao,
+                       int lbra, int lket, const Gamma& gm, long nao, int strip, int natm, double* work,
+                       double* out, hipStream_t st) {
   if (hint_boys_ensure(st)) return XT_ERR_HIP;
-  GradTerms tm;
-  tm.nterm = nterm;
-  for (int t = 0; t < kGradMaxTerms; ++t) {
-    tm.wj[t] = t < nterm ? wj[t] : 0.0;
-    tm.wk[t] = t < nterm ? wk[t] : 0.0;
-  }
   const int nstrip = (int)(((long)nket + strip - 1) / strip);   // <= nket
   const long n = (long)nbra * nstrip;
   double* partial = work;
   double* bsum = work + 3 * n;
   const int blk = 64;
   const dim3 grid((unsigned)((n + blk - 1) / blk));
-#define XT_GRAD(ML, MB)                                                                                  \
-  hipLaunchKernelGGL((k_grad_jk<ML, MB>), grid, dim3(blk), 0, st, nbra, bra_info, bra_prim, eb, bra_ao, \
-                     nket, ket_info, ket_prim, ek, ket_ao, tm, P, Q, nao, nstrip, partial)
+#define XT_GRAD(ML, MB)                                                                                   \
+  hipLaunchKernelGGL((k_grad_jk<ML, MB, Gamma>), grid, dim3(blk), 0, st, nbra, bra_info, bra_prim, eb,   \
+                     bra_ao, nket, ket_info, ket_prim, ek, ket_ao, gm, nao, nstrip, partial)
   if (lbra <= 4 && lbra + lket <= 6)   // s, p shells: (d p p | p p) 3 + 2
     XT_GRAD(6, 4);
   else if (lbra <= 6 && lbra + lket <= 10)   // d shells: (d d d | d d) 5 + 4
@@ -203,6 +222,44 @@ int grad_jk(int nbra, const int* bra_info, const double* bra_prim, const double*
   hipLaunchKernelGGL(k_grad_atoms, dim3((unsigned)((3 * natm + 63) / 64)), dim3(64), 0, st, nbra, natm, bra_ao,
                      bsum, out);
   return hipGetLastError() == hipSuccess ? 0 : XT_ERR_HIP;
+}
+
+int grad_jk(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao, int nket,
+            const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao, int lbra, int lket,
+            int nterm, const double* wj, const double* wk, const double* P, const double* Q, long nao, int strip,
+            int natm, double* work, double* out, hipStream_t st) {
+  if (nbra == 0 || nket == 0 || natm == 0) return 0;
+  GammaPairs gm;
+  gm.tm.nterm = nterm;
+  for (int t = 0; t < kGradMaxTerms; ++t) {
+    gm.tm.wj[t] = t < nterm ? wj[t] : 0.0;
+    gm.tm.wk[t] = t < nterm ? wk[t] : 0.0;
+  }
+  gm.P = P;
+  gm.Q = Q;
+  return grad_launch(nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra, lket, gm, nao,
+                     strip, natm, work, out, st);
+}
+
+int grad_jk2(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao, int nket,
+             const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao, int lbra, int lket,
+             int nj, const double* wj, const double* PJ, const double* QJ, int nk, const double* wk,
+             const double* PK, const double* QK, long nao, int strip, int natm, double* work, double* out,
+             hipStream_t st) {
+  if (nbra == 0 || nket == 0 || natm == 0) return 0;
+  GammaLists gm;
+  gm.nj = nj;
+  gm.nk = nk;
+  for (int t = 0; t < kGradMaxTerms; ++t) {
+    gm.wj[t] = t < nj ? wj[t] : 0.0;
+    gm.wk[t] = t < nk ? wk[t] : 0.0;
+  }
+  gm.PJ = nj ? PJ : nullptr;   // an empty list is never read
+  gm.QJ = nj ? QJ : nullptr;
+  gm.PK = nk ? PK : nullptr;
+  gm.QK = nk ? QK : nullptr;
+  return grad_launch(nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra, lket, gm, nao,
+                     strip, natm, work, out, st);
 }
 
 }  // namespace xt

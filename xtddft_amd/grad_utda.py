@@ -1,0 +1,339 @@
+"""Analytic nuclear gradients of U-TDA (spin-conserving TDA) states on a UHF or UKS reference: the
+reference's ``xtddft/grad_jp/grad/utdhf.py`` with Y = 0, extended to LDA / GGA functionals (pure
+or global hybrid) as PySCF's ``grad.tduks`` is,
+
+    td = XTDA(mol, mf); td.kernel()
+    g = td.nuc_grad_method()                   # UTDAGradients
+    g.state = 2                                # 1-based
+    de = g.kernel()                            # (natm, 3) Ha / Bohr, d(E_SCF + omega_state)/dR
+
+With X_s (nvir_s, nocc_s) the amplitudes of one root, |X_a|^2 + |X_b|^2 = 1, Xt_s = C_v X_s C_o^T,
+X_S = (Xt + Xt^T) / 2 and X_A = (Xt - Xt^T) / 2 per spin, the functional that is differentiated is
+
+    omega = sum_s tr(X_s^T F_vv,s X_s) - tr(X_s F_oo,s X_s^T) + X_S,tot : J[X_S,tot]
+            - hyb sum_s (X_S,s : K[X_S,s] + X_A,s : K[X_A,s]) + sum_g rho1(g) . wv[X_S](g)
+
+(hyb = 1 and no XC term on Hartree-Fock); rho1 and wv = w fxc rho1 are what ``xt_xc_resp`` returns for
+the pair (X_S,a, X_S,b).  The coupling applied to X is G_s = J[X_S,tot] - hyb K[Xt_s] + V^resp_s[X_S]
+(d omega = 2 dXt_s : G_s), and the Lagrangian follows the working spin-flip ``grad.grad_elec`` with
+-hyb K[X] replaced by G_s and both blocks of T in both spins:
+
+    T_s        = C_v X X^T C_v^T - C_o X^T X C_o^T
+    veff0doo_s = J[T_a + T_b] - hyb K[T_s] + the potential of wv[T] + wv2,   wv2 = w d(rho1^T fxc rho1)/d rho0
+    rhs_s      = 2 (C_v^T veff0doo_s C_o + G_vv^T X - X G_oo^T)              (Z-vector, ``qc.grad.solve_zvector``)
+    W_oo = F_oo + C_o^T (veff0doo + veff[Z^S]) C_o - X^T X F_oo + X^T G_vo,   W_vv = X X^T F_vv + X G_vo^T,
+    W_vo = Z F_oo + 2 X G_oo^T.
+
+wv2 is the third functional derivative contracted twice with rho1 (PySCF's ``k1ao``): two directional
+derivatives of the energy density and one backward pass (``qc.xc.kernel_grad_torch``), no
+third-derivative tensor.  The two-electron derivative term is ONE ``xt_grad_jk2`` call
+(``qc.grad.grad_jk_lists``) with, for D = D0 + T + Z^S and TZ = T + Z^S per spin,
+
+    Coulomb list:   (+1; D_tot, D_tot), (-1; TZ_tot, TZ_tot), (+2; X_S,tot, X_S,tot)
+    exchange list:  per spin, scaled by hyb: (-1; D_s, D_s), (+1; TZ_s, TZ_s) and the X_S / X_A exchange
+                    4 hyb (X_S[a,c] X_S[b,d] + X_A[a,c] X_A[b,d]) = 2 hyb (Xt[a,c] Xt[b,d] + Xt^T[a,c] Xt^T[b,d])
+
+in the weights of ``qc.grad.jk_terms``: three Coulomb and eight exchange pairs on a hybrid, none of
+the latter on a pure functional.  The XC nuclear-derivative term (``qc.grad.grad_xc_pairs``) is
+G_xc[w vxc[rho0]; D0 + T + Z^S] + G_xc[wv[T + Z^S] + wv2; D0] + G_xc[2 wv[X_S]; X_S] on a grid held fixed
+in space.
+
+Refused with NotImplementedError: an ROKS / ROHF mean field (X-TDA: the reference's ``xtdhf.py``),
+``basis='tensor'``, a Kohn-Sham mean field on the host, and everything ``qc.grad.check_gradient_mf`` /
+``check_ks_gradient_mf`` refuse (meta-GGA, range separation, VV10, density fitting, X2C).
+"""
+from __future__ import annotations
+
+import time
+
+import numpy as np
+
+from .qc import grad as _g
+
+
+def _scf_of(td):
+    """(the SCF object behind ``td.mf``, whether it is a Kohn-Sham reference) after every refusal."""
+    mf = td.mf
+    if getattr(td, "X", False) or getattr(mf, "is_rohf", False):
+        raise NotImplementedError("X-TDA gradients on an ROKS / ROHF reference (the reference's grad_jp/grad/xtdhf.py) "
+                                  "are not built: the restricted open-shell determinant is not variational in the "
+                                  "rotations the U-TDA formula assumes; use a UHF / UKS reference")
+    if td.basis == 'tensor':
+        raise NotImplementedError("U-TDA gradients need basis='orbital': the tensor-basis solver is not built")
+    ref = mf.extra.get("qc_scf") if hasattr(mf, "extra") else None
+    scf = ref() if ref is not None else None          # a weak reference: the mean field does not own the SCF
+    if scf is None:
+        raise ValueError("the gradient needs the SCF object the mean field came from (qc UHF / UKS .to_meanfield()), "
+                         "still alive")
+    if str(getattr(scf, "xc", "HF")).upper() == "HF":
+        _g.check_gradient_mf(scf)
+        return scf, False
+    if getattr(scf, "_device", None) is None:
+        raise NotImplementedError(f"U-TDA gradients for xc = {scf.xc!r} on the host: the XC derivative (xt_grad_xc) "
+                                  "and the XC response (xt_xc_resp) have no host path; call mf.to_device() before "
+                                  "the SCF")
+    _g.check_ks_gradient_mf(scf)
+    return scf, True
+
+
+def utda_amplitudes(td, state_idx):
+    """(X_a (nvir_a, nocc_a), X_b (nvir_b, nocc_b)) of root ``state_idx`` (0-based), normalised to
+    |X_a|^2 + |X_b|^2 = 1: ``td.v`` holds [CV(aa) | OV(aa) | CO(bb) | CV(bb)] (``XTDA._split_blocks``); the
+    alpha part is already (occupied, virtual) row-major, the beta part goes back through ``td.order``."""
+    v = np.asarray(td.v)[:, state_idx]
+    nc, no, nv = td.nc, td.no, td.nv
+    na = (nc + no) * nv
+    xa = v[:na].reshape(nc + no, nv)
+    b = np.zeros(nc * (no + nv))
+    b[np.asarray(td.order)[na:] - na] = v[na:]
+    xb = b.reshape(nc, no + nv)
+    nrm = np.linalg.norm(v)
+    return xa.T / nrm, xb.T / nrm
+
+
+class KSTerms:
+    """The XC terms of ``grad_elec`` on a UKS reference (LDA / GGA), everything in the order alpha, beta:
+    the response potential and weights of the reference (``DeviceEngine.fxc_response``), the
+    third-derivative weights wv2 (``qc.xc.kernel_grad_torch``) and the XC nuclear-derivative terms
+    (``qc.grad.grad_xc_pairs``)."""
+
+    def __init__(self, scf, timings, xc_chunk=None):
+        self.scf, self.tm = scf, timings
+        self.eng = scf.device_engine
+        if self.eng is None:
+            raise RuntimeError("the XC terms run on the GPU: run the SCF after mf.to_device()")
+        self.xc_chunk = xc_chunk
+        self.de_xc = None
+        self.x_s = self.wv1 = self.wv2 = None
+        self.vresp = self._count(_g.ks_response(scf))     # J - hyb K + V^resp: one call of the response
+        self.tm["xc_response_s"] = 0.0
+        self.tm["xc_response_calls"] = 0
+
+    def _count(self, f):
+        def timed(*a, **kw):
+            t0 = time.perf_counter()
+            out = f(*a, **kw)
+            self.tm["xc_response_s"] += time.perf_counter() - t0
+            self.tm["xc_response_calls"] += 1
+            return out
+        return timed
+
+    def coupling(self, x_s):
+        """V^resp (2, nao, nao) of the symmetric transition densities X_S; keeps wv1 = wv[X_S] and
+        wv2 = w d(rho1^T fxc rho1) / d rho0 for ``vxc_resp_t`` and ``grad``."""
+        import torch
+        from .qc import xc as _xc
+        eng = self.eng
+        out = self._count(eng.fxc_response)(x_s, want=("v", "wv", "rho1"))
+        t0 = time.perf_counter()
+        nk = 4 if eng.xctype == "GGA" else 1
+        with torch.cuda.device(eng.dev):
+            # rho0 through the engine's own GEMM (a fixed summation order): equal calls give equal bits
+            rho0 = eng.rho(np.asarray([c[:, o > 0] @ c[:, o > 0].T for c, o in zip(self.scf.mo_coeff, self.scf.mo_occ)]))
+            _, dq = _xc.kernel_grad_torch(self.scf.xc, rho0[:, :nk], out["rho1"][:, :nk])
+            wv2 = torch.zeros_like(out["wv"])
+            wv2[:, :nk] = dq * eng.w
+        torch.cuda.synchronize(eng.dev)
+        self.tm["kernel_grad_s"] = time.perf_counter() - t0
+        self.x_s, self.wv1, self.wv2 = np.asarray(x_s), out["wv"], wv2
+        return out["v"]
+
+    def vxc_resp_t(self, dm):
+        """f^xc[T] and the potential of wv2, from one row pass (potentials are linear in their weights)."""
+        wv = self._count(self.eng.fxc_response)(np.asarray(dm), want=("wv",))["wv"]
+        t0 = time.perf_counter()
+        v = self.eng.rows_potential(wv + self.wv2)
+        self.tm["xc_rows_s"] = time.perf_counter() - t0
+        return v
+
+    def grad(self, d0, tz):
+        """G_xc[w vxc[rho0]; D0 + T + Z^S] + G_xc[wv[T + Z^S] + wv2; D0] + G_xc[2 wv[X_S]; X_S], (natm, 3)."""
+        import torch
+        from .qc import xc as _xc
+        eng = self.eng
+        d0, tz = np.asarray(d0), np.asarray(tz)
+        wv = self._count(eng.fxc_response)(tz, want=("wv",))["wv"]
+        t0 = time.perf_counter()
+        with torch.cuda.device(eng.dev):
+            h0 = _xc.eval_xc_eff_torch(self.scf.xc, eng.rho(d0), deriv=1)[1] * eng.w
+        st = {}
+        pairs = [(h0, d0 + tz), (wv + self.wv2, d0), (2.0 * self.wv1, self.x_s)]
+        de = _g.grad_xc_pairs(self.scf, pairs, chunk=self.xc_chunk, stats=st)
+        self.tm["grad_xc_s"] = time.perf_counter() - t0
+        self.tm["grad_xc_stats"] = st
+        self.de_xc = de
+        return de
+
+
+def jk_lists(d, tz, xt, hyb):
+    """(Coulomb list [(wj, P, Q)], exchange list [(wk, P, Q)]) of the two-electron derivative term:
+    d, tz, xt (2, nao, nao) = D0 + T + Z^S, T + Z^S and Xt = C_v X C_o^T per spin (module docstring)."""
+    dt, tzt = d[0] + d[1], tz[0] + tz[1]
+    xst = sum((m + m.T) * 0.5 for m in xt)
+
+    def j(c, m):
+        wj, _, p, q = _g.jk_terms(c, 0, m, m)
+        return (wj, p, q)
+
+    def k(c, m):
+        _, wk, p, q = _g.jk_terms(0, c, m, m)
+        return (wk, p, q)
+    jl = [j(1, dt), j(-1, tzt), j(2, xst)]
+    kl = []
+    if hyb != 0:
+        for s in range(2):
+            kl += [k(-hyb, d[s]), k(hyb, tz[s]), (2.0 * hyb, xt[s], xt[s]), (2.0 * hyb, xt[s].T, xt[s].T)]
+    return jl, kl
+
+
+def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None, hyb=1.0, xc=None, one_call=True):
+    """Electronic part of the gradient of E_SCF + omega, (natm, 3).  ``x`` = (X_a, X_b), each
+    (nvir_s, nocc_s); ``hyb``: the fraction of exact exchange (1 for Hartree-Fock); ``xc``: the XC terms
+    of a UKS reference (``KSTerms``), None for Hartree-Fock.  ``one_call``: the two-electron derivative
+    term as one ``xt_grad_jk2`` call; False sends the same pairs as two ``xt_grad_jk`` calls."""
+    tm = {} if timings is None else timings
+    mol = scf.mol
+    C = [np.asarray(scf.mo_coeff[s]) for s in range(2)]
+    occ = [np.asarray(scf.mo_occ[s]) > 0 for s in range(2)]
+    o = [C[s][:, occ[s]] for s in range(2)]
+    v = [C[s][:, ~occ[s]] for s in range(2)]
+    no = [o[s].shape[1] for s in range(2)]
+    fock_ao = scf.get_hcore()[None] + np.asarray(scf._veff)       # a UKS _veff holds V_xc
+    F = [C[s].T @ fock_ao[s] @ C[s] for s in range(2)]
+    x = [np.asarray(x[s], dtype=np.float64) for s in range(2)]
+    for s in range(2):
+        if x[s].shape != (v[s].shape[1], no[s]):
+            raise ValueError(f"amplitude shape {x[s].shape}, expected {(v[s].shape[1], no[s])}")
+
+    def get_jk(dms):
+        dms = np.asarray(dms)
+        if hyb == 0:             # a pure functional forms no exchange
+            return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], np.zeros_like(dms)
+        vj, vk = scf.get_jk(dm=dms, hermi=0)
+        return vj, (vk if hyb == 1 else hyb * vk)
+
+    too = [-x[s].T @ x[s] for s in range(2)]
+    tvv = [x[s] @ x[s].T for s in range(2)]
+    dmt = np.asarray([v[s] @ tvv[s] @ v[s].T + o[s] @ too[s] @ o[s].T for s in range(2)])
+    dmt = (dmt + dmt.transpose(0, 2, 1)) * 0.5
+    xt = np.asarray([v[s] @ x[s] @ o[s].T for s in range(2)])
+    xs = (xt + xt.transpose(0, 2, 1)) * 0.5
+    vj, vk = get_jk((dmt[0], dmt[1], xt[0], xt[1]))               # vk carries hyb from here on
+    jx = vj[2] + vj[3]                                            # J[Xt_tot] = J[X_S,tot]
+    jx = (jx + jx.T) * 0.5
+    G = [jx - vk[2 + s] for s in range(2)]
+    veff0doo = [vj[0] + vj[1] - vk[s] for s in range(2)]
+    if xc is not None:
+        vx = xc.coupling(xs)
+        fxt = xc.vxc_resp_t(dmt)
+        G = [G[s] + vx[s] for s in range(2)]
+        veff0doo = [veff0doo[s] + fxt[s] for s in range(2)]
+    gmo = [C[s].T @ G[s] @ C[s] for s in range(2)]
+    # right-hand side of the Z-vector equations
+    wvo = [2.0 * (v[s].T @ veff0doo[s] @ o[s] + gmo[s][no[s]:, no[s]:].T @ x[s] - x[s] @ gmo[s][:no[s], :no[s]].T)
+           for s in range(2)]
+    t0 = time.perf_counter()
+    za, zb, res, ncyc = _g.solve_zvector(scf, wvo[0], wvo[1], cphf_conv_tol, cphf_max_cycle,
+                                         vresp=None if xc is None else xc.vresp)
+    tm["zvector_s"] = time.perf_counter() - t0
+    tm["zvector_cycles"], tm["zvector_residual"] = ncyc, float(res)
+    z = [za, zb]
+    z1ao = np.asarray([v[s] @ z[s] @ o[s].T for s in range(2)])
+    zs = (z1ao + z1ao.transpose(0, 2, 1)) * 0.5
+    veff = _g.hf_response(scf)(zs) if xc is None else xc.vresp(zs)      # J - hyb K (+ V^resp) of Z^S
+    # energy-weighted density W
+    im0 = 0.0
+    for s in range(2):
+        n = no[s]
+        w = np.zeros_like(F[s])
+        w[:n, :n] = (F[s][:n, :n] + o[s].T @ (veff0doo[s] + veff[s]) @ o[s] + too[s] @ F[s][:n, :n]
+                     + x[s].T @ gmo[s][n:, :n])
+        w[n:, n:] = tvv[s] @ F[s][n:, n:].T + x[s] @ gmo[s][n:, :n].T
+        w[n:, :n] = z[s] @ F[s][:n, :n].T + 2.0 * x[s] @ gmo[s][:n, :n].T
+        im0 = im0 + C[s] @ w @ C[s].T
+    d0 = np.asarray([o[s] @ o[s].T for s in range(2)])
+    tz = zs + dmt
+    t0 = time.perf_counter()
+    de = _g.contract_1e(mol, _g.hcore_generator(mol), _g.get_ovlp(mol), (d0 + tz).sum(axis=0), im0)
+    tm["one_electron_s"] = time.perf_counter() - t0
+    jl, kl = jk_lists(d0 + tz, tz, xt, hyb)
+    t0 = time.perf_counter()
+    st = {}
+    if one_call:
+        de += _g.grad_jk_lists(mol, jl, kl, device, stats=st)
+    else:
+        for terms in two_call_terms(jl, kl):
+            de += _g.grad_jk_device(mol, terms, device, stats=st)
+    tm["grad_jk_s"] = time.perf_counter() - t0
+    tm["buckets"] = st.get("buckets", [])
+    if xc is not None:
+        de += xc.grad(d0, tz)
+    return de
+
+
+def two_call_terms(jl, kl):
+    """The pairs of ``jk_lists`` as the terms of ``xt_grad_jk`` calls of at most eight pairs each (every
+    pair with one zero weight): what a gradient without ``xt_grad_jk2`` would have to send."""
+    terms = [(w, 0.0, p, q) for w, p, q in jl] + [(0.0, w, p, q) for w, p, q in kl]
+    return [terms[i:i + _g.MAX_TERMS] for i in range(0, len(terms), _g.MAX_TERMS)]
+
+
+class UTDAGradients:
+    """``XTDA(mol, mf).nuc_grad_method()`` on a UHF or UKS (LDA / GGA, pure or global hybrid, on a
+    device) reference, with the attributes of ``grad.SFGradients``: ``state`` (1-based),
+    ``cphf_conv_tol``, ``cphf_max_cycle``, ``atmlst``, ``xc_chunk``, ``de``.  ``timings`` of the last
+    gradient: ``one_electron_s``, ``grad_jk_s`` and ``buckets``, ``zvector_s`` / ``zvector_cycles`` /
+    ``zvector_residual`` and, on a UKS reference, ``xc_response_s`` / ``xc_response_calls`` (every
+    V^resp / wv evaluation, the Z-vector's included), ``kernel_grad_s`` (the third-derivative weights),
+    ``xc_rows_s`` and ``grad_xc_s``."""
+
+    cphf_max_cycle = 500
+    cphf_conv_tol = 1e-10
+
+    def __init__(self, td):
+        self.base = td
+        self._scf, self.is_ks = _scf_of(td)
+        self.mol = self._scf.mol
+        self.state = 1
+        self.atmlst = None
+        self.de = None
+        self.de_xc = None        # the XC nuclear-derivative part of the last gradient (UKS reference)
+        self.xc_chunk = None     # grid points per xt_grad_xc call; None: qc.grad.default_xc_chunk
+        self.timings = {}
+
+    def grad_nuc(self, mol=None, atmlst=None):
+        return _g.grad_nuc(mol or self.mol, atmlst)
+
+    def grad_elec(self, atmlst=None):
+        td = self.base
+        if getattr(td, "v", None) is None:
+            raise ValueError("run the XTDA kernel() first")
+        if not 1 <= self.state <= np.asarray(td.v).shape[1]:
+            raise ValueError(f"state {self.state} is not among the computed roots")
+        conv = getattr(td, "converged", None)
+        if td.use_Davidson and conv is not None and not bool(np.asarray(conv)[self.state - 1]):
+            raise RuntimeError(f"root {self.state} of the Davidson solve is not converged")
+        dev = getattr(self._scf, "_device", None)
+        if dev is None:
+            raise RuntimeError("the gradient runs on the GPU (xt_grad_jk2, device J / K): call "
+                               "mf.to_device() before the SCF")
+        self.timings.clear()
+        x = utda_amplitudes(td, self.state - 1)
+        if self.is_ks:
+            xc = KSTerms(self._scf, self.timings, self.xc_chunk)
+            de = grad_elec(self._scf, x, dev, self.cphf_conv_tol, self.cphf_max_cycle, self.timings,
+                           hyb=float(self._scf.hyb), xc=xc)
+            self.de_xc = xc.de_xc
+        else:
+            de = grad_elec(self._scf, x, dev, self.cphf_conv_tol, self.cphf_max_cycle, self.timings)
+        return de if atmlst is None else de[list(atmlst)]
+
+    def kernel(self, state=None, atmlst=None):
+        if state is not None:
+            self.state = state
+        if atmlst is None:
+            atmlst = self.atmlst
+        else:
+            self.atmlst = atmlst
+        self.de = self.grad_elec(atmlst) + self.grad_nuc(atmlst=atmlst)
+        return self.de

@@ -232,13 +232,14 @@ class DeviceEngine:
         ``xt_xc_resp`` call (rho1, wv = w fxc rho1 and b_s, csrc/xt_xc_resp.hip) and the GEMMs
         phi^T b_s.  ``want``: "v" -- the response potential V^resp (2, nao, nao), a host array, phi^T b
         plus its transpose for GGA (the conventions of ``vxc``); "wv" -- the unhalved weights
-        (2, 4, G) on the device, planes 1..3 zero for LDA.  Returns a dict.  ``stats`` receives the
+        (2, 4, G) on the device, planes 1..3 zero for LDA; "rho1" -- the response density and its gradient
+        (2, 4, G) on the device likewise.  Returns a dict.  ``stats`` receives the
         seconds of the GEMMs and of the kernel and the bytes the kernel moved."""
         import time
         torch = self.torch
-        unknown = set(want) - {"v", "wv"}
+        unknown = set(want) - {"v", "wv", "rho1"}
         if unknown or not want:
-            raise ValueError(f"fxc_response: want is any of 'v', 'wv', got {tuple(want)}")
+            raise ValueError(f"fxc_response: want is any of 'v', 'wv', 'rho1', got {tuple(want)}")
         fxc = self.fxc_ground()
         from .grad import default_xc_chunk
         gga = self.xctype == "GGA"
@@ -247,12 +248,13 @@ class DeviceEngine:
         chunk = default_xc_chunk(n, ng) if self.fxc_chunk is None else int(self.fxc_chunk)
         if chunk < 1:
             raise ValueError("chunk must be at least 1")
-        need_v, need_wv = "v" in want, "wv" in want
+        need_v, need_wv, need_r = "v" in want, "wv" in want, "rho1" in want
         d = torch.as_tensor(np.ascontiguousarray(np.asarray(dms, dtype=np.float64)), device=self.dev)
         if d.shape != (2, n, n):
             raise ValueError(f"fxc_response: densities of shape {tuple(d.shape)}, expected {(2, n, n)}")
         kw = dict(dtype=torch.float64, device=self.dev)
         wv = torch.zeros((2, 4, ng), **kw) if need_wv else None
+        r1 = torch.zeros((2, 4, ng), **kw) if need_r else None
         v = torch.zeros((2, n, n), **kw) if need_v else None
         tg = tk = 0.0
         nbytes = 0
@@ -275,7 +277,8 @@ class DeviceEngine:
                     t0 = time.perf_counter()
                 _capi.check(self.L.xt_xc_resp(m, n, _capi.XC[self.xctype], a0.data_ptr(), ao.stride(0), n,
                                               c.data_ptr(), n, fxc[..., g0:].data_ptr(), ng, self.w[g0:].data_ptr(),
-                                              None, wv[..., g0:].data_ptr() if need_wv else None, ng,
+                                              r1[..., g0:].data_ptr() if need_r else None,
+                                              wv[..., g0:].data_ptr() if need_wv else None, ng,
                                               b.data_ptr() if need_v else None, n, st), "xt_xc_resp")
                 if stats is not None:
                     torch.cuda.synchronize(self.dev)
@@ -301,6 +304,8 @@ class DeviceEngine:
             out["v"] = v.cpu().numpy()
         if need_wv:
             out["wv"] = wv
+        if need_r:
+            out["rho1"] = r1
         return out
 
     # ------------------------------------------------------------ spin-flip channel, given weights

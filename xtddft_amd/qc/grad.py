@@ -14,6 +14,8 @@
   PySCF's ``vj[x,i,j] = -(d_x i j|k l) D[l,k]``, ``vk[x,i,l] = -(d_x i j|k l) D[j,k]`` and
   ``de_A += sum_{p on A, q} v[x,p,q] (D'[p,q] + D'[q,p])`` are the terms
   (wj, wk, P, Q) = (-1, 0, D' + D'^T, D^T) and (0, -1, D' + D'^T, D) (``jk_terms``);
+* ``grad_jk_lists`` -- the same contraction with separate Coulomb and exchange pair lists
+  (``xt_grad_jk2``), for the two-particle densities of more than eight pairs (``xtddft_amd/grad_utda.py``);
 * ``solve_zvector`` -- the UCPHF Z-vector equations (usfcis.py:127-150) by a host-driven
   preconditioned GMRES whose response J / K come from ``DeviceEngine.get_jk``;
 * ``Gradients`` -- ``UHF.nuc_grad_method()``: the T = Z = X = 0 subset of the excited-state
@@ -221,27 +223,19 @@ def work_size(nbra, nket, strip):
     return 3 * nbra * ((nket + strip - 1) // strip + 1)
 
 
-def grad_jk_device(mol, terms, device: int = 0, strip=None, stats=None):
-    """(natm, 3): sum over ``terms`` = [(wj, wk, P, Q)] (P, Q (nao, nao) over the spherical AOs,
-    arbitrary) of the derivative-ERI contraction in the module docstring, through ``xt_grad_jk``.
-    The bra tables (``ints.deriv_tables``) hold the derivative with respect to the centre of a, so
-    the kernel's sum is negated here.  The densities are transformed to the Cartesian components once; the launches of the
-    (bra bucket, ket bucket) ranges add into one (natm, 3) array in a fixed order.
-    ``stats``: a dict that receives quartets and wall ms per bucket pair."""
+def _launch_buckets(mol, device, strip, stats, name, make_call):
+    """The launches both entries of the kernel share: for every (bra bucket, ket bucket) range of the
+    tables one call with its own workspace, all adding into one (natm, 3) array in a fixed order, whose
+    negative is returned (the bra tables hold the derivative with respect to the centre of a).
+    ``make_call(dv, tab)`` puts the densities on the device and returns ``call(head, tail)``: the C entry
+    with the table arguments ``head``, its own density arguments, and ``tail`` (nao, strip, natm, work,
+    nwork, out, stream).  ``stats``: a dict that receives quartets and wall ms per bucket pair."""
     import torch
-    if not 1 <= len(terms) <= MAX_TERMS:
-        raise ValueError(f"xt_grad_jk takes 1..{MAX_TERMS} terms, got {len(terms)}")
-    L = _capi.lib()
     tab = grad_tables(mol)
     dv = torch.device(f"cuda:{device}")
-    C = tab.cmat
-    wj = np.array([t[0] for t in terms], dtype=np.float64)
-    wk = np.array([t[1] for t in terms], dtype=np.float64)
-    P = np.stack([C.T @ np.asarray(t[2], dtype=np.float64) @ C for t in terms])
-    Q = np.stack([C.T @ np.asarray(t[3], dtype=np.float64) @ C for t in terms])
     with torch.cuda.device(dv):
         b, k, g = tab.bra.dev(device), tab.ket.dev(device), tab.dev(device)
-        tP, tQ = torch.as_tensor(P, device=dv), torch.as_tensor(Q, device=dv)
+        call = make_call(dv, tab)
         out = torch.zeros((mol.natm, 3), dtype=torch.float64, device=dv)
         st = ctypes.c_void_p(torch.cuda.current_stream(dv).cuda_stream)
         for b0, b1, lb in tab.bra_ranges:
@@ -253,18 +247,76 @@ def grad_jk_device(mol, terms, device: int = 0, strip=None, stats=None):
                 if stats is not None:
                     torch.cuda.synchronize(dv)
                     t0 = time.perf_counter()
-                _capi.check(L.xt_grad_jk(nb, b["info"][b0:].data_ptr(), b["prim"].data_ptr(), b["eb"].data_ptr(),
-                                         g["bra_ao"][b0:].data_ptr(), nk, g["ket_info"][k0:].data_ptr(),
-                                         k["pprim"].data_ptr(), k["eab"].data_ptr(), g["ket_ao"][k0:].data_ptr(),
-                                         lb, lk, len(terms), wj.ctypes.data, wk.ctypes.data, tP.data_ptr(),
-                                         tQ.data_ptr(), tab.ncart, sl, mol.natm, work.data_ptr(), nwork,
-                                         out.data_ptr(), st), "xt_grad_jk")
+                head = (nb, b["info"][b0:].data_ptr(), b["prim"].data_ptr(), b["eb"].data_ptr(),
+                        g["bra_ao"][b0:].data_ptr(), nk, g["ket_info"][k0:].data_ptr(), k["pprim"].data_ptr(),
+                        k["eab"].data_ptr(), g["ket_ao"][k0:].data_ptr(), lb, lk)
+                tail = (tab.ncart, sl, mol.natm, work.data_ptr(), nwork, out.data_ptr(), st)
+                _capi.check(call(head, tail), name)
                 if stats is not None:
                     torch.cuda.synchronize(dv)
                     stats.setdefault("buckets", []).append(dict(
                         bra_order=lb, ket_order=lk, quartets=nb * nk, strip=sl,
                         ms=(time.perf_counter() - t0) * 1e3))
         return -out.cpu().numpy()
+
+
+def _cart_stack(tab, dv, terms, i):
+    """The matrices ``t[i]`` of ``terms`` over the Cartesian components, stacked on the device; None
+    for an empty list."""
+    import torch
+    if not terms:
+        return None
+    C = tab.cmat
+    return torch.as_tensor(np.stack([C.T @ np.asarray(t[i], dtype=np.float64) @ C for t in terms]), device=dv)
+
+
+def grad_jk_device(mol, terms, device: int = 0, strip=None, stats=None):
+    """(natm, 3): sum over ``terms`` = [(wj, wk, P, Q)] (P, Q (nao, nao) over the spherical AOs,
+    arbitrary) of the derivative-ERI contraction in the module docstring, through ``xt_grad_jk``.
+    The bra tables (``ints.deriv_tables``) hold the derivative with respect to the centre of a, so
+    the kernel's sum is negated here.  The densities are transformed to the Cartesian components once; the launches of the
+    (bra bucket, ket bucket) ranges add into one (natm, 3) array in a fixed order.
+    ``stats``: a dict that receives quartets and wall ms per bucket pair."""
+    if not 1 <= len(terms) <= MAX_TERMS:
+        raise ValueError(f"xt_grad_jk takes 1..{MAX_TERMS} terms, got {len(terms)}")
+    L = _capi.lib()
+    wj = np.array([t[0] for t in terms], dtype=np.float64)
+    wk = np.array([t[1] for t in terms], dtype=np.float64)
+
+    def make_call(dv, tab):
+        tP, tQ = _cart_stack(tab, dv, terms, 2), _cart_stack(tab, dv, terms, 3)
+        return lambda head, tail: L.xt_grad_jk(*head, len(terms), wj.ctypes.data, wk.ctypes.data, tP.data_ptr(),
+                                               tQ.data_ptr(), *tail)
+    return _launch_buckets(mol, device, strip, stats, "xt_grad_jk", make_call)
+
+
+def grad_jk_lists(mol, jterms, kterms, device: int = 0, strip=None, stats=None):
+    """(natm, 3): ``grad_jk_device`` with a Coulomb list ``jterms`` = [(wj, P, Q)] and an exchange list
+    ``kterms`` = [(wk, P, Q)] of their own, through ``xt_grad_jk2``,
+
+        g[A, m] = sum_{a on A} sum_{bcd} (d_m a  b|c d) (sum_t wj_t P_t[a,b] Q_t[c,d] + sum_t wk_t P_t[a,c] Q_t[b,d]);
+
+    up to ``MAX_TERMS`` pairs in each list, at least one pair in all, one pass over the derivative
+    integrals.  An empty list is handed over as null pointers (a pure functional passes no exchange).
+    Sign, transformation to Cartesian components, launch order and ``stats`` as ``grad_jk_device``."""
+    jterms, kterms = list(jterms), list(kterms)
+    nj, nk = len(jterms), len(kterms)
+    if nj > MAX_TERMS or nk > MAX_TERMS or nj + nk < 1:
+        raise ValueError(f"xt_grad_jk2 takes 0..{MAX_TERMS} Coulomb and 0..{MAX_TERMS} exchange pairs, at least one "
+                         f"in all, got {nj} and {nk}")
+    L = _capi.lib()
+    wj = np.array([t[0] for t in jterms], dtype=np.float64)
+    wk = np.array([t[0] for t in kterms], dtype=np.float64)
+
+    def ptr(x):
+        return None if x is None else x.data_ptr()
+
+    def make_call(dv, tab):
+        pj, qj = _cart_stack(tab, dv, jterms, 1), _cart_stack(tab, dv, jterms, 2)
+        pk, qk = _cart_stack(tab, dv, kterms, 1), _cart_stack(tab, dv, kterms, 2)
+        return lambda head, tail: L.xt_grad_jk2(*head, nj, wj.ctypes.data if nj else None, ptr(pj), ptr(qj),
+                                                nk, wk.ctypes.data if nk else None, ptr(pk), ptr(qk), *tail)
+    return _launch_buckets(mol, device, strip, stats, "xt_grad_jk2", make_call)
 
 
 # ------------------------------------------------------------------ Z-vector

@@ -601,3 +601,59 @@ def energy_density_torch(xc: str, x):
     on = ((rs[0, 0] > DENS_THRESHOLD).to(torch.float64).detach(),
           (rs[1, 0] > DENS_THRESHOLD).to(torch.float64).detach())
     return _energy_density(comps, ra, rb, saa, sab, sbb, None, None, torch, on)
+
+
+def kernel_grad_torch(xc: str, rho0, rho1, max_points: int = 1 << 20):
+    """The density derivative of the spin-conserving kernel along a fixed response density, without the
+    third-derivative tensor (the ``k1ao`` of a U-TDA gradient): with fxc = ``eval_xc_eff_torch(xc, rho0,
+    deriv=2)[2]`` and ``rho1`` (2, ncomp, G) held fixed,
+
+        q(g)        = sum_{s k s' k'} rho1_s(k, g) fxc(s, k, s', k', g) rho1_s'(k', g)
+        dq(s, k, g) = d q(g) / d rho0_s(k, g)
+
+    Returns (q (G,), dq (2, ncomp, G)), un-weighted, torch tensors on the device of ``rho0``.  q is two
+    directional derivatives of ``energy_density_torch`` along rho1 and dq one backward pass of it, in
+    batches of ``max_points`` grid points.  The points are those ``eval_xc_eff_torch`` selects
+    (DENS_THRESHOLD on rho_a + rho_b), with its clamps and exchange flags, so q is the contraction of the
+    fxc it returns; a screened point has q = 0 and dq = 0 exactly."""
+    import torch
+    comps, _, xctype = parse_xc(xc)
+    if xctype not in ("LDA", "GGA"):
+        raise NotImplementedError(f"kernel_grad_torch covers LDA / GGA functionals, not {xctype}")
+    ncomp = NCOMP[xctype]
+    rho0 = torch.as_tensor(rho0, dtype=torch.float64)
+    if rho0.dim() == 2:
+        rho0 = rho0[:, None, :]
+    rho1 = torch.as_tensor(rho1, dtype=torch.float64, device=rho0.device)
+    if rho1.dim() == 2:
+        rho1 = rho1[:, None, :]
+    rho0, rho1 = rho0[:, :ncomp], rho1[:, :ncomp]
+    if rho0.shape != rho1.shape or rho0.shape[0] != 2:
+        raise ValueError(f"kernel_grad_torch: rho0 {tuple(rho0.shape)} and rho1 {tuple(rho1.shape)}, expected "
+                         f"(2, {ncomp}, G) each")
+    ng = rho0.shape[-1]
+    kw = dict(dtype=torch.float64, device=rho0.device)
+    q = torch.zeros(ng, **kw)
+    dq = torch.zeros((2, ncomp, ng), **kw)
+    if not comps:
+        return q, dq
+    gb = max(1, int(max_points))
+    for g0 in range(0, ng, gb):
+        g1 = min(ng, g0 + gb)
+        r0 = rho0[:, :, g0:g1].detach().clone().requires_grad_(True)
+        idx = torch.nonzero((r0[0, 0] + r0[1, 0]).detach() > DENS_THRESHOLD).squeeze(1)
+        if idx.numel() == 0:
+            continue
+        x = r0[:, :, idx]
+        dirn = rho1[:, :, g0:g1][:, :, idx]
+        eps = energy_density_torch(xc, x)
+        if not torch.is_tensor(eps) or not eps.requires_grad:
+            continue
+        d1 = (torch.autograd.grad(eps.sum(), x, create_graph=True)[0] * dirn).sum((0, 1))
+        d2 = (torch.autograd.grad(d1.sum(), x, create_graph=True)[0] * dirn).sum((0, 1))
+        q[g0:g1] = torch.zeros(g1 - g0, **kw).index_add(0, idx, d2.detach())
+        if d2.requires_grad:
+            g = torch.autograd.grad(d2.sum(), r0, allow_unused=True)[0]
+            if g is not None:
+                dq[:, :, g0:g1] = g
+    return q, dq

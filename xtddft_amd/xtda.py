@@ -170,6 +170,13 @@ class XTDA:
         self.dS2 = self.deltaS2()
         return self.e
 
+    def nuc_grad_method(self):
+        """Analytic nuclear gradients of the U-TDA roots on a UHF / UKS reference
+        (``grad_utda.UTDAGradients``, the reference's ``grad_jp/grad/utdhf.py`` with Y = 0); an ROKS
+        reference (X-TDA) is refused there."""
+        from .grad_utda import UTDAGradients
+        return UTDAGradients(self)
+
     # ---------------------------------------------------------- properties
     def _split_blocks(self):
         nc, no, nv = self.nc, self.no, self.nv
