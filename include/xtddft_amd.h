@@ -583,6 +583,21 @@ int xt_grad_jk2(int nbra, const int* bra_info, const double* bra_prim, const dou
                 int lbra, int lket, int nj, const double* wj, const double* pj, const double* qj, int nk,
                 const double* wk, const double* pk, const double* qk, long nao, int strip, int natm,
                 double* work, long nwork, double* out, void* hip_stream);
+/* xt_grad_jk2 with the derivative integrals (d_m a b|c d) taken over erf(omega r12) / r12, the long-range
+   operator of a range-separated hybrid (CAM-B3LYP, wB97X-D): the same Gamma over the same tables.  Per
+   primitive quartet with alpha = p s / (p + s) the Hermite integrals are those of
+   a2 = alpha omega^2 / (alpha + omega^2) times sqrt(a2 / alpha), the formula of xt_int2e_cart; the Boys
+   table, the image, the Gamma cache, the strips and the reduction are xt_grad_jk2's (one kernel body,
+   the operator a compile-time parameter).  The exchange of such a functional is
+   hyb K + (alpha - hyb) K_LR, so its gradient is two calls: xt_grad_jk2 with the Coulomb list and the
+   exchange list weighted by hyb, and xt_grad_jk2_lr with nj = 0 and the same exchange pairs weighted
+   by alpha - hyb.  Arguments, limits and errors as xt_grad_jk2; omega must be finite and > 0 (1/r12
+   is xt_grad_jk2).  Equal inputs give equal bits. */
+int xt_grad_jk2_lr(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao,
+                   int nket, const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao,
+                   int lbra, int lket, int nj, const double* wj, const double* pj, const double* qj, int nk,
+                   const double* wk, const double* pk, const double* qk, long nao, int strip, int natm,
+                   double* work, long nwork, double* out, void* hip_stream, double omega);
 /* AO values (deriv 0) or values and gradients (deriv 1) of normalised spherical
    AOs on grid points (PySCF mol.eval_ao / ni.block_loop, SF_TDA.py:63-68, the AO
    input of cache_xc_kernel / nr_uks_fxc, XTDA.py:504,514), device pointers:

@@ -34,7 +34,7 @@ EXPORTS = [
     "xt_set_nlc", "xt_vv10_ground", "xt_vv10_response",
     "xt_stda_charges", "xt_stda_half", "xt_stda_diag", "xt_stda_select", "xt_stda_matrix",
     "xt_si_couple", "xt_hint_cart", "xt_grad_jk", "xt_grad_xc", "xt_xc_resp",
-    "xt_xc_resp_sf", "xt_xc_rows", "xt_grad_jk2",
+    "xt_xc_resp_sf", "xt_xc_rows", "xt_grad_jk2", "xt_grad_jk2_lr",
 ]
 
 
@@ -176,6 +176,7 @@ def lib():
                              c_int, c_int, dp, c_long, dp, vp]
     L.xt_grad_jk2.argtypes = [c_int, vp, dp, dp, vp, c_int, vp, dp, dp, vp, c_int, c_int, c_int, dp, dp, dp, c_int, dp,
                               dp, dp, c_long, c_int, c_int, dp, c_long, dp, vp]
+    L.xt_grad_jk2_lr.argtypes = L.xt_grad_jk2.argtypes + [c_double]
     L.xt_grad_xc.argtypes = [c_int, dp, c_int, vp, dp, dp, dp, vp, c_int, c_int, c_int, c_int, c_int, dp, dp, dp,
                              c_long, dp, c_long, dp, vp]
     L.xt_xc_resp.argtypes = [c_long, c_int, c_int, dp, c_long, c_long, dp, c_long, dp, c_long, dp, dp, dp, c_long,

@@ -2,6 +2,7 @@
 // GEMM engine (xt_dgemm*, xt_gemm_plan / xt_gemm_run), the Davidson helper kernels and the
 // integral / AO evaluators.  Host code only: argument checks in front of the launchers.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <vector>
 #include "xt_host.h"
 #include "xt_kernels.h"
@@ -206,30 +207,56 @@ extern "C" int xt_grad_jk(int nbra, const int* bra_info, const double* bra_prim,
   return r ? fail(r, "grad_jk launch failed") : 0;
 }
 
+// xt_grad_jk2 (omega = 0: 1/r12) and xt_grad_jk2_lr (omega > 0: erf(omega r12) / r12): one set of checks,
+// every message under the entry's own name
+static int grad_jk2_entry(const char* what, int nbra, const int* bra_info, const double* bra_prim, const double* eb,
+                          const int* bra_ao, int nket, const int* ket_info, const double* ket_prim,
+                          const double* ek, const int* ket_ao, int lbra, int lket, int nj, const double* wj,
+                          const double* pj, const double* qj, int nk, const double* wk, const double* pk,
+                          const double* qk, long nao, int strip, int natm, double* work, long nwork, double* out,
+                          void* stream, double omega) {
+  const std::string pre = err_prefix(what);
+  if (nbra < 0 || nket < 0 || nao < 0 || natm < 0 || nwork < 0) return fail(XT_ERR_ARG, pre + "negative size");
+  if (strip < 1) return fail(XT_ERR_ARG, pre + "strip must be at least 1");
+  if (lbra < 0 || lket < 0 || lbra > kHintMaxLBra || lbra + lket > kHintMaxL)
+    return fail(XT_ERR_ARG, pre + "bra order <= 8 and total order <= 14");
+  if (nj < 0 || nj > kGradMaxTerms) return fail(XT_ERR_ARG, pre + "nj must be 0..8");
+  if (nk < 0 || nk > kGradMaxTerms) return fail(XT_ERR_ARG, pre + "nk must be 0..8");
+  if (nj + nk < 1) return fail(XT_ERR_ARG, pre + "nj and nk are both zero");
+  if (nj > 0 && !wj) return fail(XT_ERR_ARG, pre + "null wj with nj > 0");
+  if (nk > 0 && !wk) return fail(XT_ERR_ARG, pre + "null wk with nk > 0");
+  if (nbra == 0 || nket == 0 || natm == 0) return 0;   // nothing to add
+  if (nj > 0 && (!pj || !qj)) return fail(XT_ERR_ARG, pre + "null pj or qj with nj > 0");
+  if (nk > 0 && (!pk || !qk)) return fail(XT_ERR_ARG, pre + "null pk or qk with nk > 0");
+  if (!bra_info || !bra_prim || !eb || !bra_ao || !ket_info || !ket_prim || !ek || !ket_ao || !work || !out)
+    return fail(XT_ERR_ARG, pre + "null table, workspace or output");
+  if (nwork < grad_jk_work(nbra, nket, strip)) return fail(XT_ERR_ARG, pre + "workspace too small");
+  const int r = grad_jk2(nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra, lket, nj, wj,
+                         pj, qj, nk, wk, pk, qk, nao, strip, natm, work, out, (hipStream_t)stream, omega);
+  return r ? fail(r, omega > 0.0 ? "grad_jk2_lr launch failed" : "grad_jk2 launch failed") : 0;
+}
+
 extern "C" int xt_grad_jk2(int nbra, const int* bra_info, const double* bra_prim, const double* eb,
                            const int* bra_ao, int nket, const int* ket_info, const double* ket_prim,
                            const double* ek, const int* ket_ao, int lbra, int lket, int nj, const double* wj,
                            const double* pj, const double* qj, int nk, const double* wk, const double* pk,
                            const double* qk, long nao, int strip, int natm, double* work, long nwork, double* out,
                            void* stream) {
-  if (nbra < 0 || nket < 0 || nao < 0 || natm < 0 || nwork < 0) return fail(XT_ERR_ARG, "xt_grad_jk2: negative size");
-  if (strip < 1) return fail(XT_ERR_ARG, "xt_grad_jk2: strip must be at least 1");
-  if (lbra < 0 || lket < 0 || lbra > kHintMaxLBra || lbra + lket > kHintMaxL)
-    return fail(XT_ERR_ARG, "xt_grad_jk2: bra order <= 8 and total order <= 14");
-  if (nj < 0 || nj > kGradMaxTerms) return fail(XT_ERR_ARG, "xt_grad_jk2: nj must be 0..8");
-  if (nk < 0 || nk > kGradMaxTerms) return fail(XT_ERR_ARG, "xt_grad_jk2: nk must be 0..8");
-  if (nj + nk < 1) return fail(XT_ERR_ARG, "xt_grad_jk2: nj and nk are both zero");
-  if (nj > 0 && !wj) return fail(XT_ERR_ARG, "xt_grad_jk2: null wj with nj > 0");
-  if (nk > 0 && !wk) return fail(XT_ERR_ARG, "xt_grad_jk2: null wk with nk > 0");
-  if (nbra == 0 || nket == 0 || natm == 0) return 0;   // nothing to add
-  if (nj > 0 && (!pj || !qj)) return fail(XT_ERR_ARG, "xt_grad_jk2: null pj or qj with nj > 0");
-  if (nk > 0 && (!pk || !qk)) return fail(XT_ERR_ARG, "xt_grad_jk2: null pk or qk with nk > 0");
-  if (!bra_info || !bra_prim || !eb || !bra_ao || !ket_info || !ket_prim || !ek || !ket_ao || !work || !out)
-    return fail(XT_ERR_ARG, "xt_grad_jk2: null table, workspace or output");
-  if (nwork < grad_jk_work(nbra, nket, strip)) return fail(XT_ERR_ARG, "xt_grad_jk2: workspace too small");
-  const int r = grad_jk2(nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra, lket, nj, wj,
-                         pj, qj, nk, wk, pk, qk, nao, strip, natm, work, out, (hipStream_t)stream);
-  return r ? fail(r, "grad_jk2 launch failed") : 0;
+  return grad_jk2_entry("xt_grad_jk2", nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra,
+                        lket, nj, wj, pj, qj, nk, wk, pk, qk, nao, strip, natm, work, nwork, out, stream, 0.0);
+}
+
+extern "C" int xt_grad_jk2_lr(int nbra, const int* bra_info, const double* bra_prim, const double* eb,
+                              const int* bra_ao, int nket, const int* ket_info, const double* ket_prim,
+                              const double* ek, const int* ket_ao, int lbra, int lket, int nj, const double* wj,
+                              const double* pj, const double* qj, int nk, const double* wk, const double* pk,
+                              const double* qk, long nao, int strip, int natm, double* work, long nwork, double* out,
+                              void* stream, double omega) {
+  // a caller who wants 1/r12 uses xt_grad_jk2: zero, negative, NaN and inf are all refused
+  if (!(omega > 0.0) || !std::isfinite(omega))
+    return fail(XT_ERR_ARG, "xt_grad_jk2_lr: omega must be finite and > 0");
+  return grad_jk2_entry("xt_grad_jk2_lr", nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao,
+                        lbra, lket, nj, wj, pj, qj, nk, wk, pk, qk, nao, strip, natm, work, nwork, out, stream, omega);
 }
 
 extern "C" int xt_eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info,

@@ -7,7 +7,10 @@
 //   Gamma_abcd = sum_{t < nterm} wj[t] P_t[a,b] Q_t[c,d] + wk[t] P_t[a,c] Q_t[b,d]           (xt_grad_jk)
 //   Gamma_abcd = sum_{t < nj} wj[t] PJ_t[a,b] QJ_t[c,d] + sum_{t < nk} wk[t] PK_t[a,c] QK_t[b,d]   (xt_grad_jk2)
 //
-// One kernel body serves both: k_grad_jk is a template over the functor that forms Gamma.
+//   the same Gamma with (d_m a b | c d) over erf(omega r12) / r12                                 (xt_grad_jk2_lr)
+//
+// One kernel body serves all three: k_grad_jk is a template over the functor that forms Gamma and over
+// the operator (Coulomb: 1/r12; ErfLR: the long-range part of a range-separated hybrid's exchange).
 //
 // d_m a is what the bra table holds (qc/ints.py deriv_tables: the derivative with respect to the
 // centre of a, the negative of the electron-coordinate derivative; the host fixes the sign);
@@ -79,13 +82,30 @@ struct GammaLists {
   }
 };
 
+// The operator of the integrals, a compile-time parameter of k_grad_jk.  Coulomb is 1/r12 and holds
+// nothing: its instantiations are the kernel without any of the lines below `if constexpr`.  ErfLR is
+// erf(omega r12) / r12 by the formula of xt_int.hip (qc/ints.py _attenuate): per primitive quartet with
+// alpha = p s / (p + s), the Hermite integrals at a2 = alpha w^2 / (alpha + w^2) times sqrt(a2 / alpha).
+struct Coulomb {
+  static constexpr bool kAttenuated = false;
+};
+struct ErfLR {
+  static constexpr bool kAttenuated = true;
+  double w2;   // omega^2
+};
+// What the kernel takes by value: the Gamma functor and the operator's data in one argument.  Coulomb is
+// an empty base, so GradArgs<Gamma, Coulomb> has the layout of Gamma and the 1/r12 instantiations keep
+// their kernel arguments as they were.
+template <class Gamma, class Op>
+struct GradArgs : Gamma, Op {};
+
 // MAXL: largest total order, MAXLB: largest bra order (they size R / S and M)
-template <int MAXL, int MAXLB, class Gamma>
+template <int MAXL, int MAXLB, class Gamma, class Op>
 __global__ void __launch_bounds__(64)
 k_grad_jk(int nbra, const int* __restrict__ bra_info, const double* __restrict__ bra_prim,
           const double* __restrict__ eb, const int* __restrict__ bra_ao, int nket,
           const int* __restrict__ ket_info, const double* __restrict__ ket_prim, const double* __restrict__ ek,
-          const int* __restrict__ ket_ao, Gamma gm, long nao, int nstrip, double* __restrict__ partial) {
+          const int* __restrict__ ket_ao, GradArgs<Gamma, Op> gm, long nao, int nstrip, double* __restrict__ partial) {
   const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= (long)nbra * nstrip) return;
   const int s = (int)(id / nbra), k = (int)(id % nbra);
@@ -119,8 +139,13 @@ k_grad_jk(int nbra, const int* __restrict__ bra_info, const double* __restrict__
       for (int r = 0; r < nr; ++r) {
         const double* cp = ket_prim + 4 * (long)(kr0 + r);
         const double sx = cp[0];
-        hint_r<MAXL>(L, p * sx / (p + sx), pp[1] - cp[1], pp[2] - cp[2], pp[3] - cp[3], R, S);
-        const double pref = 2.0 * pow(M_PI, 2.5) / (p * sx * sqrt(p + sx));
+        double alpha = p * sx / (p + sx);
+        if constexpr (Op::kAttenuated) alpha = alpha * gm.w2 / (alpha + gm.w2);   // a2
+        hint_r<MAXL>(L, alpha, pp[1] - cp[1], pp[2] - cp[2], pp[3] - cp[3], R, S);
+        double pref = 2.0 * pow(M_PI, 2.5) / (p * sx * sqrt(p + sx));
+        // the R's times sqrt(a2 / alpha) = sqrt(w^2 / (alpha + w^2)), through pref (R enters linearly);
+        // formed after hint_r so that nothing more is live across it
+        if constexpr (Op::kAttenuated) pref *= sqrt(gm.w2 / (p * sx / (p + sx) + gm.w2));
         for (int c = 0; c < ncol; ++c) {
           // M[t] = sum_u (-1)^{|u|} E^c_u(r) R[t + u]
           const double* e = ek + ke0 + ((long)c * ntk) * nr + r;
@@ -191,12 +216,12 @@ long grad_jk_work(int nbra, int nket, int strip) {
   return 3 * (long)nbra * (nstrip + 1);
 }
 
-// the three launches of one call, for either way of forming Gamma
-template <class Gamma>
+// the three launches of one call, for either way of forming Gamma and either operator
+template <class Gamma, class Op>
 static int grad_launch(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao,
                        int nket, const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao,
                        int lbra, int lket, const Gamma& gm, long nao, int strip, int natm, double* work,
-                       double* out, hipStream_t st) {
+                       double* out, hipStream_t st, const Op& op) {
   if (hint_boys_ensure(st)) return XT_ERR_HIP;
   const int nstrip = (int)(((long)nket + strip - 1) / strip);   // <= nket
   const long n = (long)nbra * nstrip;
@@ -204,9 +229,10 @@ static int grad_launch(int nbra, const int* bra_info, const double* bra_prim, co
   double* bsum = work + 3 * n;
   const int blk = 64;
   const dim3 grid((unsigned)((n + blk - 1) / blk));
+  const GradArgs<Gamma, Op> ga{gm, op};
 #define XT_GRAD(ML, MB)                                                                                   \
-  hipLaunchKernelGGL((k_grad_jk<ML, MB, Gamma>), grid, dim3(blk), 0, st, nbra, bra_info, bra_prim, eb,   \
-                     bra_ao, nket, ket_info, ket_prim, ek, ket_ao, gm, nao, nstrip, partial)
+  hipLaunchKernelGGL((k_grad_jk<ML, MB, Gamma, Op>), grid, dim3(blk), 0, st, nbra, bra_info, bra_prim,  \
+                     eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, ga, nao, nstrip, partial)
   if (lbra <= 4 && lbra + lket <= 6)   // s, p shells: (d p p | p p) 3 + 2
     XT_GRAD(6, 4);
   else if (lbra <= 6 && lbra + lket <= 10)   // d shells: (d d d | d d) 5 + 4
@@ -238,14 +264,15 @@ int grad_jk(int nbra, const int* bra_info, const double* bra_prim, const double*
   gm.P = P;
   gm.Q = Q;
   return grad_launch(nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra, lket, gm, nao,
-                     strip, natm, work, out, st);
+                     strip, natm, work, out, st, Coulomb{});
 }
 
+// omega == 0: 1/r12 (xt_grad_jk2); omega > 0: erf(omega r12) / r12 (xt_grad_jk2_lr)
 int grad_jk2(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao, int nket,
              const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao, int lbra, int lket,
              int nj, const double* wj, const double* PJ, const double* QJ, int nk, const double* wk,
              const double* PK, const double* QK, long nao, int strip, int natm, double* work, double* out,
-             hipStream_t st) {
+             hipStream_t st, double omega) {
   if (nbra == 0 || nket == 0 || natm == 0) return 0;
   GammaLists gm;
   gm.nj = nj;
@@ -258,8 +285,11 @@ int grad_jk2(int nbra, const int* bra_info, const double* bra_prim, const double
   gm.QJ = nj ? QJ : nullptr;
   gm.PK = nk ? PK : nullptr;
   gm.QK = nk ? QK : nullptr;
+  if (omega > 0.0)
+    return grad_launch(nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra, lket, gm,
+                       nao, strip, natm, work, out, st, ErfLR{omega * omega});
   return grad_launch(nbra, bra_info, bra_prim, eb, bra_ao, nket, ket_info, ket_prim, ek, ket_ao, lbra, lket, gm, nao,
-                     strip, natm, work, out, st);
+                     strip, natm, work, out, st, Coulomb{});
 }
 
 }  // namespace xt

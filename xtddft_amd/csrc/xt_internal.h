@@ -183,12 +183,13 @@ int grad_jk(int nbra, const int* bra_info, const double* bra_prim, const double*
             int nterm, const double* wj, const double* wk, const double* P, const double* Q, long nao, int strip,
             int natm, double* work, double* out, hipStream_t st);
 // the same contraction with a Coulomb list (nj pairs) and an exchange list (nk pairs) of their own, each
-// up to kGradMaxTerms; a list whose count is zero is not read
+// up to kGradMaxTerms; a list whose count is zero is not read.  omega = 0: the integrals over 1/r12;
+// omega > 0: over erf(omega r12) / r12 (the same kernel body, instantiated for the operator)
 int grad_jk2(int nbra, const int* bra_info, const double* bra_prim, const double* eb, const int* bra_ao, int nket,
              const int* ket_info, const double* ket_prim, const double* ek, const int* ket_ao, int lbra, int lket,
              int nj, const double* wj, const double* PJ, const double* QJ, int nk, const double* wk,
              const double* PK, const double* QK, long nao, int strip, int natm, double* work, double* out,
-             hipStream_t st);
+             hipStream_t st, double omega = 0.0);
 int eval_ao(int ngrid, const double* coords, int nshell, const int* shell_info, const double* dat,
             const double* sph, const double* norm, int deriv, double* out, long ldo, long comp_stride,
             hipStream_t st);

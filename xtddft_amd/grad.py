@@ -38,6 +38,12 @@ refusing method = 1 and names them.
 Refused with NotImplementedError: on a UHF reference method != 0; on a UKS reference method = 0
 (the ALDA0 kernel's density derivative), a mean field on the host, and everything ``qc.grad.check_ks_gradient_mf`` refuses
 (meta-GGA, range-separated, VV10, ROKS); density fitting, X2C and an ROHF reference on either.
+
+Range-separated hybrids (CAM-B3LYP, wB97X-D) come in through ``td.Gradients(state=1)``,
+which builds the same objects with ``allow_rsh=True``: every K above is hyb K + (alpha - hyb) K_LR (the one
+``get_jk`` closure of ``grad_elec`` and ``qc.grad.ks_response``), and the kernel pairs go as two lists through
+``xt_grad_jk2`` and ``xt_grad_jk2_lr`` (``qc.grad.grad_jk_rsh``).  ``nuc_grad_method()``, ``SFU_gradient(td)`` and
+``SFD_gradient(td)`` with default arguments keep refusing them.
 """
 from __future__ import annotations
 
@@ -48,9 +54,10 @@ import numpy as np
 from .qc import grad as _g
 
 
-def _scf_of(td, multicollinear=False):
+def _scf_of(td, multicollinear=False, allow_rsh=False):
     """(the SCF object behind ``td.mf``, whether it is a Kohn-Sham reference) after every refusal.
-    ``multicollinear``: the caller is ``SFU_gradient`` / ``SFD_gradient``, which take method = 1."""
+    ``multicollinear``: the caller is ``SFU_gradient`` / ``SFD_gradient``, which take method = 1;
+    ``allow_rsh``: the caller came through ``.Gradients()``, which takes range-separated hybrids."""
     mf = td.mf
     if getattr(mf, "is_rohf", False):
         raise NotImplementedError("spin-flip gradients need a UHF / UKS reference (the reference's "
@@ -72,7 +79,7 @@ def _scf_of(td, multicollinear=False):
         raise NotImplementedError(f"spin-flip gradients for xc = {scf.xc!r} on the host: the XC derivative "
                                   "(xt_grad_xc) and the XC response (xt_xc_resp) have no host path; call "
                                   "mf.to_device() before the SCF")
-    _g.check_ks_gradient_mf(scf)
+    _g.check_ks_gradient_mf(scf, allow_rsh=allow_rsh)
     if td.method == 0:
         raise NotImplementedError("spin-flip gradients with the ALDA0 kernel (method = 0) on a functional: the "
                                   "density derivative of the ALDA0 kernel is not built (method = 2 is)")
@@ -208,11 +215,28 @@ class KSTerms:
         return de
 
 
-def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None, hyb=1.0, xc=None):
+OMEGA_TOL = 1e-9         # Ha: how closely the omega of the gradient's own coupling must reproduce the TDA root
+
+
+def check_root(what, omega, root):
+    """The excitation energy the gradient's coupling gives for the amplitudes against the root of the TDA
+    solve: they differ when the operator's exchange and the gradient's do (a missing long-range term)."""
+    if abs(omega - root) > OMEGA_TOL:
+        raise AssertionError(f"{what}: the coupling of the gradient gives omega = {omega:.12f} Ha for these "
+                             f"amplitudes, the TDA root is {root:.12f} Ha (difference {omega - root:.3e} > "
+                             f"{OMEGA_TOL:.0e}): the gradient would not be the derivative of that root")
+
+
+def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None, hyb=1.0, xc=None,
+              rsh=None, root=None):
     """Electronic part of the gradient of E_SCF + omega, (natm, 3).  ``x_ab`` (nvir_b, nocc_a) in
     the labels of spin-flip-down; ``flip``: the state is spin-flip-up, and "a" below is beta.
     ``hyb``: the fraction of exact exchange (1 for Hartree-Fock) on every K; ``xc``: the XC terms of a
-    UKS reference (``KSTerms``), None for Hartree-Fock, which then runs exactly the UHF formula."""
+    UKS reference (``KSTerms``), None for Hartree-Fock, which then runs exactly the UHF formula.
+    ``rsh``: (omega, alpha) of a range-separated hybrid, whose exchange is hyb K + (alpha - hyb) K_LR in
+    every place K stands below (all of them go through ``get_jk``) and in the kernel lists
+    (``qc.grad.grad_jk_rsh``); ``root``: the TDA root (Ha) these amplitudes belong to, checked against the
+    omega of the coupling formed here (``check_root``)."""
     tm = {} if timings is None else timings
     mol = scf.mol
     s = (1, 0) if flip else (0, 1)
@@ -227,8 +251,16 @@ def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, 
     if x_ab.shape != (orbvb.shape[1], nocca):
         raise ValueError(f"amplitude shape {x_ab.shape}, expected {(orbvb.shape[1], nocca)}")
 
+    k_lr = 0.0 if rsh is None else float(rsh[1]) - hyb
+
     def get_jk(dms):             # J / K do not depend on which spin a density belongs to
         dms = np.asarray(dms)
+        if k_lr != 0:            # hyb K + (alpha - hyb) K_LR; get_k_lr takes non-symmetric densities
+            vk_lr = k_lr * np.asarray(scf.get_k_lr(dms))
+            if hyb == 0:
+                return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], vk_lr
+            vj, vk = scf.get_jk(dm=dms, hermi=0)
+            return vj, hyb * vk + vk_lr
         if hyb == 0:             # a pure functional forms no exchange
             return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], np.zeros_like(dms)
         vj, vk = scf.get_jk(dm=dms, hermi=0)
@@ -247,6 +279,9 @@ def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, 
     if vsf is not None:
         kx = kx - vsf
     vkmo = mo_coeff[1].T @ kx @ mo_coeff[0]                       # beta rows, alpha columns
+    if root is not None:         # omega = x . (F_vv x - x F_oo - K[X]_vo)
+        check_root("spin-flip gradient", float(np.sum(x_ab * (
+            fockbmo[noccb:, noccb:] @ x_ab - x_ab @ fockamo[:nocca, :nocca] - vkmo[noccb:, :nocca]))), float(root))
     veff0dooa = vj[0] + vj[1] - vk[0]
     veff0doob = vj[0] + vj[1] - vk[1]
     if xc is not None:           # f^xc[T] (+ V^k)
@@ -287,14 +322,21 @@ def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, 
     da, db = oo0a + dmz1dooa, oo0b + dmz1doob
     tz = dmz1dooa + dmz1doob
     terms = [_g.jk_terms(1, 0, da + db, da + db), _g.jk_terms(-1, 0, tz, tz)]
-    if hyb != 0:
-        terms += [_g.jk_terms(0, -hyb, da, da), _g.jk_terms(0, hyb, dmz1dooa, dmz1dooa),
-                  _g.jk_terms(0, -hyb, db, db), _g.jk_terms(0, hyb, dmz1doob, dmz1doob),
-                  _g.jk_terms(0, -2 * hyb, dmSx, dmSx),
-                  (0.0, 2.0 * hyb, dmAx - dmAx.T, dmAx)]       # -2 hyb vk[X_A] . (X_A[p,q] - X_A[q,p])
+    kw = hyb if rsh is None else 1.0     # range-separated: the pairs of full exchange, weighted per operator below
+    if kw != 0:
+        terms += [_g.jk_terms(0, -kw, da, da), _g.jk_terms(0, kw, dmz1dooa, dmz1dooa),
+                  _g.jk_terms(0, -kw, db, db), _g.jk_terms(0, kw, dmz1doob, dmz1doob),
+                  _g.jk_terms(0, -2 * kw, dmSx, dmSx),
+                  (0.0, 2.0 * kw, dmAx - dmAx.T, dmAx)]        # -2 hyb vk[X_A] . (X_A[p,q] - X_A[q,p])
     t0 = time.perf_counter()
     st = {}
-    de += _g.grad_jk_device(mol, terms, device, stats=st)
+    if rsh is None:
+        de += _g.grad_jk_device(mol, terms, device, stats=st)
+    else:                        # the same pairs as two lists: 2 Coulomb and 6 exchange pairs, two calls
+        jl, kl = _g.pair_lists(terms)
+        de += _g.grad_jk_rsh(mol, jl, kl, float(rsh[0]), hyb, float(rsh[1]), device, stats=st)
+        tm["grad_jk_full_s"], tm["grad_jk_lr_s"] = st.get("full_s"), st.get("lr_s")
+        tm["buckets_lr"] = st.get("buckets_lr", [])
     tm["grad_jk_s"] = time.perf_counter() - t0
     tm["buckets"] = st.get("buckets", [])
     if xc is not None:
@@ -333,9 +375,9 @@ class SFGradients:
 
     _multicollinear = False      # SFU_gradient / SFD_gradient: method = 1 is accepted
 
-    def __init__(self, td):
+    def __init__(self, td, *, allow_rsh=False):
         self.base = td
-        self._scf, self.is_ks = _scf_of(td, self._multicollinear)
+        self._scf, self.is_ks = _scf_of(td, self._multicollinear, allow_rsh)
         # the multicollinear kernel is differentiated at the sample count the roots were computed with
         self.collinear_samples = None
         if td.method == 1:
@@ -370,8 +412,11 @@ class SFGradients:
             self.timings.clear()
             mc = dict(mf=td.mf, samples=self.collinear_samples) if td.method == 1 else None
             xc = KSTerms(self._scf, (1, 0) if flip else (0, 1), self.timings, self.xc_chunk, mc=mc)
+            omega = float(getattr(self._scf, "omega", 0.0))
+            rsh = (omega, float(self._scf.alpha)) if omega != 0 else None
+            root = float(np.asarray(td.e)[self.state - 1]) if rsh is not None else None
             de = grad_elec(self._scf, sf_amplitude(td, self.state - 1), flip, dev, self.cphf_conv_tol,
-                           self.cphf_max_cycle, self.timings, hyb=float(self._scf.hyb), xc=xc)
+                           self.cphf_max_cycle, self.timings, hyb=float(self._scf.hyb), xc=xc, rsh=rsh, root=root)
             self.de_xc = xc.de_xc
         else:
             de = grad_elec(self._scf, sf_amplitude(td, self.state - 1), flip, dev, self.cphf_conv_tol,
@@ -396,7 +441,7 @@ class _SFKernelGradient(SFGradients):
     _multicollinear = True
     _td_class = None
 
-    def __init__(self, td, method=1, state=1):
+    def __init__(self, td, method=1, state=1, *, allow_rsh=False):
         from . import sf_tda
         want = getattr(sf_tda, self._td_class)
         if not isinstance(td, want):
@@ -407,7 +452,7 @@ class _SFKernelGradient(SFGradients):
         if method == 0:
             raise NotImplementedError("spin-flip gradients with the ALDA0 kernel (method = 0) are not built "
                                       "(grad_hb/tduks_sfu.py raises likewise); methods 1 and 2 are")
-        super().__init__(td)
+        super().__init__(td, allow_rsh=allow_rsh)
         self.method = method
         self.state = state
 

@@ -41,6 +41,11 @@ in space.
 Refused with NotImplementedError: an ROKS / ROHF mean field (X-TDA: the reference's ``xtdhf.py``),
 ``basis='tensor'``, a Kohn-Sham mean field on the host, and everything ``qc.grad.check_gradient_mf`` /
 ``check_ks_gradient_mf`` refuse (meta-GGA, range separation, VV10, density fitting, X2C).
+
+Range-separated hybrids come in through ``td.Gradients(state=1)``, which constructs
+``UTDAGradients(td, allow_rsh=True)``: -hyb K above becomes -(hyb K + (alpha - hyb) K_LR) everywhere, and the
+exchange list goes once through ``xt_grad_jk2`` weighted by hyb and once through ``xt_grad_jk2_lr`` weighted
+by alpha - hyb (``qc.grad.grad_jk_rsh``).  ``nuc_grad_method()`` keeps refusing them.
 """
 from __future__ import annotations
 
@@ -51,8 +56,9 @@ import numpy as np
 from .qc import grad as _g
 
 
-def _scf_of(td):
-    """(the SCF object behind ``td.mf``, whether it is a Kohn-Sham reference) after every refusal."""
+def _scf_of(td, allow_rsh=False):
+    """(the SCF object behind ``td.mf``, whether it is a Kohn-Sham reference) after every refusal.
+    ``allow_rsh``: the caller came through ``.Gradients()``, which takes range-separated hybrids."""
     mf = td.mf
     if getattr(td, "X", False) or getattr(mf, "is_rohf", False):
         raise NotImplementedError("X-TDA gradients on an ROKS / ROHF reference (the reference's grad_jp/grad/xtdhf.py) "
@@ -72,7 +78,7 @@ def _scf_of(td):
         raise NotImplementedError(f"U-TDA gradients for xc = {scf.xc!r} on the host: the XC derivative (xt_grad_xc) "
                                   "and the XC response (xt_xc_resp) have no host path; call mf.to_device() before "
                                   "the SCF")
-    _g.check_ks_gradient_mf(scf)
+    _g.check_ks_gradient_mf(scf, allow_rsh=allow_rsh)
     return scf, True
 
 
@@ -186,11 +192,16 @@ def jk_lists(d, tz, xt, hyb):
     return jl, kl
 
 
-def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None, hyb=1.0, xc=None, one_call=True):
+def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None, hyb=1.0, xc=None, one_call=True,
+              rsh=None, root=None):
     """Electronic part of the gradient of E_SCF + omega, (natm, 3).  ``x`` = (X_a, X_b), each
     (nvir_s, nocc_s); ``hyb``: the fraction of exact exchange (1 for Hartree-Fock); ``xc``: the XC terms
     of a UKS reference (``KSTerms``), None for Hartree-Fock.  ``one_call``: the two-electron derivative
-    term as one ``xt_grad_jk2`` call; False sends the same pairs as two ``xt_grad_jk`` calls."""
+    term as one ``xt_grad_jk2`` call; False sends the same pairs as two ``xt_grad_jk`` calls.
+    ``rsh``: (omega, alpha) of a range-separated hybrid: every K below is hyb K + (alpha - hyb) K_LR
+    (``get_jk`` here, ``qc.grad.ks_response`` in the Z-vector) and the exchange list goes once per operator
+    (``qc.grad.grad_jk_rsh``); ``root``: the TDA root (Ha) of these amplitudes, checked against the omega of
+    the coupling formed here (``grad.check_root``)."""
     tm = {} if timings is None else timings
     mol = scf.mol
     C = [np.asarray(scf.mo_coeff[s]) for s in range(2)]
@@ -205,8 +216,16 @@ def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=N
         if x[s].shape != (v[s].shape[1], no[s]):
             raise ValueError(f"amplitude shape {x[s].shape}, expected {(v[s].shape[1], no[s])}")
 
+    k_lr = 0.0 if rsh is None else float(rsh[1]) - hyb
+
     def get_jk(dms):
         dms = np.asarray(dms)
+        if k_lr != 0:            # hyb K + (alpha - hyb) K_LR; get_k_lr takes non-symmetric densities
+            vk_lr = k_lr * np.asarray(scf.get_k_lr(dms))
+            if hyb == 0:
+                return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], vk_lr
+            vj, vk = scf.get_jk(dm=dms, hermi=0)
+            return vj, hyb * vk + vk_lr
         if hyb == 0:             # a pure functional forms no exchange
             return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], np.zeros_like(dms)
         vj, vk = scf.get_jk(dm=dms, hermi=0)
@@ -229,6 +248,11 @@ def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=N
         G = [G[s] + vx[s] for s in range(2)]
         veff0doo = [veff0doo[s] + fxt[s] for s in range(2)]
     gmo = [C[s].T @ G[s] @ C[s] for s in range(2)]
+    if root is not None:         # omega = sum_s tr(X^T F_vv X) - tr(X F_oo X^T) + Xt_s : G_s
+        from .grad import check_root
+        check_root("U-TDA gradient", float(sum(np.sum(x[s] * (
+            F[s][no[s]:, no[s]:] @ x[s] - x[s] @ F[s][:no[s], :no[s]] + gmo[s][no[s]:, :no[s]])) for s in range(2))),
+            float(root))
     # right-hand side of the Z-vector equations
     wvo = [2.0 * (v[s].T @ veff0doo[s] @ o[s] + gmo[s][no[s]:, no[s]:].T @ x[s] - x[s] @ gmo[s][:no[s], :no[s]].T)
            for s in range(2)]
@@ -256,10 +280,14 @@ def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=N
     t0 = time.perf_counter()
     de = _g.contract_1e(mol, _g.hcore_generator(mol), _g.get_ovlp(mol), (d0 + tz).sum(axis=0), im0)
     tm["one_electron_s"] = time.perf_counter() - t0
-    jl, kl = jk_lists(d0 + tz, tz, xt, hyb)
+    jl, kl = jk_lists(d0 + tz, tz, xt, hyb if rsh is None else 1.0)
     t0 = time.perf_counter()
     st = {}
-    if one_call:
+    if rsh is not None:          # the pairs of full exchange, weighted per operator: two calls
+        de += _g.grad_jk_rsh(mol, jl, kl, float(rsh[0]), hyb, float(rsh[1]), device, stats=st)
+        tm["grad_jk_full_s"], tm["grad_jk_lr_s"] = st.get("full_s"), st.get("lr_s")
+        tm["buckets_lr"] = st.get("buckets_lr", [])
+    elif one_call:
         de += _g.grad_jk_lists(mol, jl, kl, device, stats=st)
     else:
         for terms in two_call_terms(jl, kl):
@@ -290,9 +318,9 @@ class UTDAGradients:
     cphf_max_cycle = 500
     cphf_conv_tol = 1e-10
 
-    def __init__(self, td):
+    def __init__(self, td, *, allow_rsh=False):
         self.base = td
-        self._scf, self.is_ks = _scf_of(td)
+        self._scf, self.is_ks = _scf_of(td, allow_rsh)
         self.mol = self._scf.mol
         self.state = 1
         self.atmlst = None
@@ -321,8 +349,11 @@ class UTDAGradients:
         x = utda_amplitudes(td, self.state - 1)
         if self.is_ks:
             xc = KSTerms(self._scf, self.timings, self.xc_chunk)
+            omega = float(getattr(self._scf, "omega", 0.0))
+            rsh = (omega, float(self._scf.alpha)) if omega != 0 else None
+            root = float(np.asarray(td.e)[self.state - 1]) if rsh is not None else None
             de = grad_elec(self._scf, x, dev, self.cphf_conv_tol, self.cphf_max_cycle, self.timings,
-                           hyb=float(self._scf.hyb), xc=xc)
+                           hyb=float(self._scf.hyb), xc=xc, rsh=rsh, root=root)
             self.de_xc = xc.de_xc
         else:
             de = grad_elec(self._scf, x, dev, self.cphf_conv_tol, self.cphf_max_cycle, self.timings)

@@ -16,6 +16,8 @@
   (wj, wk, P, Q) = (-1, 0, D' + D'^T, D^T) and (0, -1, D' + D'^T, D) (``jk_terms``);
 * ``grad_jk_lists`` -- the same contraction with separate Coulomb and exchange pair lists
   (``xt_grad_jk2``), for the two-particle densities of more than eight pairs (``xtddft_amd/grad_utda.py``);
+* ``grad_jk_rsh`` -- the two calls of a range-separated hybrid: ``xt_grad_jk2`` with hyb on the exchange
+  list and ``xt_grad_jk2_lr`` (erf(omega r12) / r12) with alpha - hyb on the same pairs;
 * ``solve_zvector`` -- the UCPHF Z-vector equations (usfcis.py:127-150) by a host-driven
   preconditioned GMRES whose response J / K come from ``DeviceEngine.get_jk``;
 * ``Gradients`` -- ``UHF.nuc_grad_method()``: the T = Z = X = 0 subset of the excited-state
@@ -290,7 +292,7 @@ def grad_jk_device(mol, terms, device: int = 0, strip=None, stats=None):
     return _launch_buckets(mol, device, strip, stats, "xt_grad_jk", make_call)
 
 
-def grad_jk_lists(mol, jterms, kterms, device: int = 0, strip=None, stats=None):
+def grad_jk_lists(mol, jterms, kterms, device: int = 0, strip=None, stats=None, omega: float = 0.0):
     """(natm, 3): ``grad_jk_device`` with a Coulomb list ``jterms`` = [(wj, P, Q)] and an exchange list
     ``kterms`` = [(wk, P, Q)] of their own, through ``xt_grad_jk2``,
 
@@ -298,12 +300,18 @@ def grad_jk_lists(mol, jterms, kterms, device: int = 0, strip=None, stats=None):
 
     up to ``MAX_TERMS`` pairs in each list, at least one pair in all, one pass over the derivative
     integrals.  An empty list is handed over as null pointers (a pure functional passes no exchange).
-    Sign, transformation to Cartesian components, launch order and ``stats`` as ``grad_jk_device``."""
+    Sign, transformation to Cartesian components, launch order and ``stats`` as ``grad_jk_device``.
+    ``omega`` > 0: the derivative integrals over erf(omega r12) / r12, through ``xt_grad_jk2_lr`` (the
+    long-range exchange of a range-separated hybrid, ``grad_jk_rsh``); the default 0 is 1/r12."""
     jterms, kterms = list(jterms), list(kterms)
     nj, nk = len(jterms), len(kterms)
+    omega = float(omega)
+    name = "xt_grad_jk2_lr" if omega > 0 else "xt_grad_jk2"
     if nj > MAX_TERMS or nk > MAX_TERMS or nj + nk < 1:
-        raise ValueError(f"xt_grad_jk2 takes 0..{MAX_TERMS} Coulomb and 0..{MAX_TERMS} exchange pairs, at least one "
+        raise ValueError(f"{name} takes 0..{MAX_TERMS} Coulomb and 0..{MAX_TERMS} exchange pairs, at least one "
                          f"in all, got {nj} and {nk}")
+    if not (np.isfinite(omega) and omega >= 0.0):
+        raise ValueError(f"omega must be finite and >= 0, got {omega!r}")
     L = _capi.lib()
     wj = np.array([t[0] for t in jterms], dtype=np.float64)
     wk = np.array([t[0] for t in kterms], dtype=np.float64)
@@ -314,9 +322,57 @@ def grad_jk_lists(mol, jterms, kterms, device: int = 0, strip=None, stats=None):
     def make_call(dv, tab):
         pj, qj = _cart_stack(tab, dv, jterms, 1), _cart_stack(tab, dv, jterms, 2)
         pk, qk = _cart_stack(tab, dv, kterms, 1), _cart_stack(tab, dv, kterms, 2)
-        return lambda head, tail: L.xt_grad_jk2(*head, nj, wj.ctypes.data if nj else None, ptr(pj), ptr(qj),
-                                                nk, wk.ctypes.data if nk else None, ptr(pk), ptr(qk), *tail)
-    return _launch_buckets(mol, device, strip, stats, "xt_grad_jk2", make_call)
+
+        def lists():             # the closure keeps the device matrices alive for as long as the call exists
+            return (nj, wj.ctypes.data if nj else None, ptr(pj), ptr(qj),
+                    nk, wk.ctypes.data if nk else None, ptr(pk), ptr(qk))
+        if omega > 0:
+            return lambda head, tail: L.xt_grad_jk2_lr(*head, *lists(), *tail, omega)
+        return lambda head, tail: L.xt_grad_jk2(*head, *lists(), *tail)
+    return _launch_buckets(mol, device, strip, stats, name, make_call)
+
+
+def pair_lists(terms):
+    """``grad_jk_device`` terms [(wj, wk, P, Q)] as the two lists of ``grad_jk_lists``: (Coulomb list
+    [(wj, P, Q)] of the terms with wj != 0, exchange list [(wk, P, Q)] of those with wk != 0)."""
+    return ([(wj, p, q) for wj, _, p, q in terms if wj != 0], [(wk, p, q) for _, wk, p, q in terms if wk != 0])
+
+
+def grad_jk_rsh(mol, jterms, kterms, omega, hyb, alpha, device: int = 0, strip=None, stats=None):
+    """(natm, 3): the two-electron derivative term of a range-separated hybrid, whose exchange is
+    hyb K + (alpha - hyb) K_LR (``qc/scf.py`` ``get_veff``).  ``jterms`` = [(wj, P, Q)] and ``kterms`` =
+    [(wk, P, Q)] are the lists of ``grad_jk_lists`` with the exchange weights of FULL exchange (hyb = 1).
+    Two passes over the derivative integrals:
+
+    1. ``xt_grad_jk2`` (1/r12) with the Coulomb list and the exchange list weighted by ``hyb``;
+    2. ``xt_grad_jk2_lr`` (erf(omega r12) / r12) with no Coulomb pair and the same exchange pairs weighted
+       by ``alpha - hyb``.
+
+    Call 2 runs alone where hyb = 0 and the Coulomb list is empty; call 1 alone where alpha = hyb.
+    ``stats``: the buckets of call 1 under ``buckets``, those of call 2 under ``buckets_lr``, and the wall
+    seconds of either under ``full_s`` / ``lr_s``."""
+    jterms, kterms = list(jterms), list(kterms)
+    if not omega > 0:
+        raise ValueError("grad_jk_rsh is for a range-separated functional (omega > 0); a global hybrid is "
+                         "one grad_jk_lists call")
+    de = np.zeros((mol.natm, 3))
+    k_full = [(hyb * w, p, q) for w, p, q in kterms] if hyb != 0 else []
+    k_lr = [((alpha - hyb) * w, p, q) for w, p, q in kterms] if alpha != hyb else []
+    if jterms or k_full:
+        st = None if stats is None else {}
+        t0 = time.perf_counter()
+        de += grad_jk_lists(mol, jterms, k_full, device, strip, st)
+        if stats is not None:
+            stats["full_s"] = time.perf_counter() - t0
+            stats.setdefault("buckets", []).extend(st.get("buckets", []))
+    if k_lr:
+        st = None if stats is None else {}
+        t0 = time.perf_counter()
+        de += grad_jk_lists(mol, [], k_lr, device, strip, st, omega=omega)
+        if stats is not None:
+            stats["lr_s"] = time.perf_counter() - t0
+            stats.setdefault("buckets_lr", []).extend(st.get("buckets", []))
+    return de
 
 
 # ------------------------------------------------------------------ Z-vector
@@ -382,16 +438,20 @@ def ks_response(mf):
     """vresp(dm (2, nao, nao) symmetric) = J[dm_a + dm_b] - hyb K[dm_s] + V^resp_s[dm]
     (``mf.gen_response(hermi=1)`` of a UKS mean field, LDA / GGA, global hybrid or pure): J / K from
     ``mf.get_jk`` and the XC response from ``DeviceEngine.fxc_response`` with fxc at the SCF
-    density.  A pure functional forms no exchange."""
+    density.  A pure functional forms no exchange; a range-separated one (``mf.omega`` != 0) adds
+    -(alpha - hyb) K_LR[dm_s] (``mf.get_k_lr``)."""
     eng = getattr(mf, "device_engine", None)
     if eng is None:
         raise RuntimeError("ks_response needs a built Kohn-Sham mean field on a device (mf.to_device())")
     hyb = float(mf.hyb)
+    k_lr = float(mf.alpha) - hyb if float(getattr(mf, "omega", 0.0)) != 0 else 0.0
     eng.fxc_ground(np.asarray(mf.make_rdm1()))
 
     def vresp(dm):
         dm = np.asarray(dm)
         vxc = eng.fxc_response(dm, want=("v",))["v"]
+        if k_lr != 0:
+            vxc = vxc - k_lr * np.asarray(mf.get_k_lr(dm))
         if hyb != 0:
             vj, vk = mf.get_jk(dm=dm, hermi=1)
             return (vj[0] + vj[1])[None] - hyb * vk + vxc
@@ -648,7 +708,8 @@ def _grad_xc_run(mf, make_items, chunk, stats):
 def ks_ground_terms(d0a, d0b, hyb):
     """The kernel terms of the UKS two-electron gradient: J[D_a + D_b] with D_a + D_b and, for a
     hybrid, -hyb K[D_s] with D_s per spin; a pure functional is the J term alone, so
-    ``xt_grad_jk`` forms no exchange contraction."""
+    ``xt_grad_jk`` forms no exchange contraction.  A range-separated functional takes the terms of
+    hyb = 1 through ``pair_lists`` and ``grad_jk_rsh``, which weights the exchange pairs per operator."""
     d0t = d0a + d0b
     terms = [jk_terms(1, 0, d0t, d0t)]
     if hyb != 0:
@@ -656,9 +717,10 @@ def ks_ground_terms(d0a, d0b, hyb):
     return terms
 
 
-def check_ks_gradient_mf(mf):
+def check_ks_gradient_mf(mf, *, allow_rsh=False):
     """The Kohn-Sham mean fields ``KSGradients`` covers: unrestricted, LDA or GGA (pure or global
-    hybrid), exact integrals, no non-local correlation."""
+    hybrid), exact integrals, no non-local correlation.  ``allow_rsh``: range-separated hybrids pass
+    (the ``.Gradients()`` doors; ``nuc_grad_method()`` keeps refusing them)."""
     if getattr(mf, "restricted_open", False):
         raise NotImplementedError("nuclear gradients need a UKS reference: an ROKS determinant is not "
                                   "variational in the rotations the formula assumes")
@@ -671,15 +733,17 @@ def check_ks_gradient_mf(mf):
                                   "potential is not built (LDA / GGA only)")
     if xctype not in ("LDA", "GGA"):
         raise NotImplementedError(f"nuclear gradients for xc = {xc!r} of type {xctype}")
-    if _xc.rsh_and_hybrid_coeff(xc)[0] != 0:
+    if _xc.rsh_and_hybrid_coeff(xc)[0] != 0 and not allow_rsh:
         raise NotImplementedError(f"nuclear gradients for the range-separated {xc!r}: xt_grad_jk has no "
-                                  "long-range (erf) operator")
+                                  "long-range (erf) operator; xt_grad_jk2_lr has, and the gradient comes from "
+                                  "the .Gradients() entry of the same object (nuc_grad_method() stays as it was)")
     if getattr(mf, "nlc", None) is not None:
         raise NotImplementedError("nuclear gradients with VV10 non-local correlation: its derivative is not built")
     if getattr(mf, "with_df", None) is not None:
         raise NotImplementedError("nuclear gradients for density-fitted mean fields")
     if getattr(mf, "with_x2c", None) is not None:
         raise NotImplementedError("nuclear gradients with the X2C core Hamiltonian")
+    # the long-range factor of a range-separated functional is built at the same chol_tol
     uses_chol = getattr(mf, "cderi_exact", None) is not None or getattr(mf, "eri_mode", "") == "cholesky"
     if uses_chol and float(getattr(mf, "chol_tol", 0.0)) > MAX_CHOL_TOL:
         raise ValueError(f"nuclear gradients need J / K of the exact integrals: Cholesky tolerance "
@@ -694,8 +758,8 @@ class KSGradients(Gradients):
     whose points and weights are held fixed, and it differs from the derivative on an
     atom-centred grid by the weight derivatives, which vanish with the grid error."""
 
-    def __init__(self, mf):
-        check_ks_gradient_mf(mf)
+    def __init__(self, mf, *, allow_rsh=False):
+        check_ks_gradient_mf(mf, allow_rsh=allow_rsh)
         self.base = mf
         self.mol = mf.mol
         self.atmlst = None
@@ -729,7 +793,14 @@ class KSGradients(Gradients):
         self.timings["one_electron_s"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         st = {}
-        de += grad_jk_device(mol, ks_ground_terms(d0a, d0b, mf.hyb), dev, stats=st)
+        omega = float(getattr(mf, "omega", 0.0))
+        if omega != 0:           # hyb K + (alpha - hyb) K_LR: the exchange pairs once per operator
+            jl, kl = pair_lists(ks_ground_terms(d0a, d0b, 1.0))
+            de += grad_jk_rsh(mol, jl, kl, omega, float(mf.hyb), float(mf.alpha), dev, stats=st)
+            self.timings["grad_jk_full_s"], self.timings["grad_jk_lr_s"] = st.get("full_s"), st.get("lr_s")
+            self.timings["buckets_lr"] = st.get("buckets_lr", [])
+        else:
+            de += grad_jk_device(mol, ks_ground_terms(d0a, d0b, mf.hyb), dev, stats=st)
         self.timings["grad_jk_s"] = time.perf_counter() - t0
         self.timings["buckets"] = st.get("buckets", [])
         t0 = time.perf_counter()

@@ -126,6 +126,16 @@ class _SCFBase:
             return KSGradients(self)
         return Gradients(self)
 
+    def Gradients(self):
+        """PySCF's other spelling of the same door, and the one that also takes the range-separated
+        hybrids (CAM-B3LYP, wB97X-D): their exchange hyb K + (alpha - hyb) K_LR is differentiated by
+        ``xt_grad_jk2`` and ``xt_grad_jk2_lr`` (``qc.grad.grad_jk_rsh``).  Every other refusal of
+        ``nuc_grad_method()`` applies here too."""
+        from .grad import Gradients, KSGradients
+        if str(self.xc).upper() != "HF" and self._device is not None:
+            return KSGradients(self, allow_rsh=True)
+        return Gradients(self)
+
     def _use_cholesky(self):
         if self.with_df is not None:
             return False

@@ -203,6 +203,19 @@ class _SFBase:
         from .grad import SFGradients
         return SFGradients(self)
 
+    def Gradients(self, state=1):
+        """The gradient of root ``state`` (1-based) by whichever entry covers this object's kernel, range-separated
+        hybrids included: method 0 on Hartree-Fock and method 2 on a functional give
+        ``grad.SFGradients``, method 1 gives ``grad.SFU_gradient`` / ``grad.SFD_gradient``.  Every other refusal
+        of those entries applies."""
+        from . import grad
+        if self.method == 1:
+            cls = grad.SFU_gradient if self.isf == 1 else grad.SFD_gradient
+            return cls(self, method=1, state=state, allow_rsh=True)
+        g = grad.SFGradients(self, allow_rsh=True)
+        g.state = state
+        return g
+
     # ------------------------------------------------ state-to-state moments
     def transition_dipoles(self, op_ao=None):
         """(ncomp, N, N) moments <i|op|j> between the ``nstates`` roots of the last

@@ -177,6 +177,15 @@ class XTDA:
         from .grad_utda import UTDAGradients
         return UTDAGradients(self)
 
+    def Gradients(self, state=1):
+        """``nuc_grad_method()`` under PySCF's other spelling, with ``state`` (1-based) set; this door also
+        takes the range-separated hybrids (``UTDAGradients(self, allow_rsh=True)``).
+        Every other refusal of ``nuc_grad_method()`` applies."""
+        from .grad_utda import UTDAGradients
+        g = UTDAGradients(self, allow_rsh=True)
+        g.state = state
+        return g
+
     # ---------------------------------------------------------- properties
     def _split_blocks(self):
         nc, no, nv = self.nc, self.no, self.nv
