@@ -25,6 +25,13 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
+def two_call_terms(jl, kl, max_terms):
+    """The pairs of ``grad_utda.jk_lists`` as the terms of ``xt_grad_jk`` calls of at most ``max_terms`` pairs
+    each (every pair with one zero weight): what a gradient without ``xt_grad_jk2`` would have to send."""
+    terms = [(w, 0.0, p, q) for w, p, q in jl] + [(0.0, w, p, q) for w, p, q in kl]
+    return [terms[i:i + max_terms] for i in range(0, len(terms), max_terms)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--molecule", default="naphthalene+")
@@ -101,13 +108,14 @@ def main():
     one = G.grad_jk_lists(mol, jl, kl, dev, stats=s1)
     one_call_s = sync() - t0
     t0 = sync()
-    two = sum(G.grad_jk_device(mol, terms, dev, stats=s2) for terms in grad_utda.two_call_terms(jl, kl))
+    calls = two_call_terms(jl, kl, G.MAX_TERMS)
+    two = sum(G.grad_jk_device(mol, terms, dev, stats=s2) for terms in calls)
     two_call_s = sync() - t0
     res["one_call_vs_two_calls"] = dict(
         coulomb_pairs=len(jl), exchange_pairs=len(kl),
         xt_grad_jk2_ms=sum(b["ms"] for b in s1["buckets"]), xt_grad_jk2_call_s=one_call_s,
         two_xt_grad_jk_ms=sum(b["ms"] for b in s2["buckets"]), two_xt_grad_jk_call_s=two_call_s,
-        calls_of_xt_grad_jk=len(grad_utda.two_call_terms(jl, kl)), max_abs_diff=float(np.abs(one - two).max()),
+        calls_of_xt_grad_jk=len(calls), max_abs_diff=float(np.abs(one - two).max()),
         max_abs=float(np.abs(one).max()), faster="xt_grad_jk2" if one_call_s < two_call_s else "two xt_grad_jk calls")
 
     # the third-derivative weights on the grid of the mean field

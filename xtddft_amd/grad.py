@@ -40,10 +40,13 @@ Refused with NotImplementedError: on a UHF reference method != 0; on a UKS refer
 (meta-GGA, range-separated, VV10, ROKS); density fitting, X2C and an ROHF reference on either.
 
 Range-separated hybrids (CAM-B3LYP, wB97X-D) come in through ``td.Gradients(state=1)``,
-which builds the same objects with ``allow_rsh=True``: every K above is hyb K + (alpha - hyb) K_LR (the one
-``get_jk`` closure of ``grad_elec`` and ``qc.grad.ks_response``), and the kernel pairs go as two lists through
-``xt_grad_jk2`` and ``xt_grad_jk2_lr`` (``qc.grad.grad_jk_rsh``).  ``nuc_grad_method()``, ``SFU_gradient(td)`` and
-``SFD_gradient(td)`` with default arguments keep refusing them.
+which builds the same objects with ``allow_rsh=True``: every K above is hyb K + (alpha - hyb) K_LR
+(``qc.grad.exchange_jk``, the ``get_jk`` of ``grad_elec``, and ``qc.grad.ks_response``), and the kernel pairs go
+as two lists through ``xt_grad_jk2`` and ``xt_grad_jk2_lr`` (``qc.grad.grad_2e``: ``grad_jk_rsh``).
+``nuc_grad_method()``, ``SFU_gradient(td)`` and ``SFD_gradient(td)`` with default arguments keep refusing them.
+
+The driver object, the XC hook and the resolution of the reference are shared with the U-TDA gradients:
+``SFGradients``, ``KSTerms`` and ``_scf_of`` build on ``grad_common``.
 """
 from __future__ import annotations
 
@@ -51,6 +54,7 @@ import time
 
 import numpy as np
 
+from . import grad_common as _c
 from .qc import grad as _g
 
 
@@ -62,24 +66,17 @@ def _scf_of(td, multicollinear=False, allow_rsh=False):
     if getattr(mf, "is_rohf", False):
         raise NotImplementedError("spin-flip gradients need a UHF / UKS reference (the reference's "
                                   "usfcis-rohf.py is not a working code path; tdroks_sfu.py is not built)")
-    ref = mf.extra.get("qc_scf") if hasattr(mf, "extra") else None
-    scf = ref() if ref is not None else None          # a weak reference: the mean field does not own the SCF
+    scf = _c.scf_behind(mf)
     if scf is None:
         if str(getattr(mf, "xctype", "HF")) != "HF":
             raise NotImplementedError(f"spin-flip gradients for xc = {mf.xc!r} need the qc UKS object the mean "
                                       "field came from (UKS.to_meanfield()), still alive")
         raise ValueError("the gradient needs the SCF object the mean field came from (qc UHF.to_meanfield()), "
                          "still alive")
-    if str(getattr(scf, "xc", "HF")).upper() == "HF":
-        if td.method != 0:
-            raise NotImplementedError("spin-flip gradients on a Hartree-Fock reference are built for method = 0 only")
-        _g.check_gradient_mf(scf)
+    if _c.is_hartree_fock(scf) and td.method != 0:
+        raise NotImplementedError("spin-flip gradients on a Hartree-Fock reference are built for method = 0 only")
+    if not _c.check_reference(scf, "spin-flip", allow_rsh):
         return scf, False
-    if getattr(scf, "_device", None) is None:
-        raise NotImplementedError(f"spin-flip gradients for xc = {scf.xc!r} on the host: the XC derivative "
-                                  "(xt_grad_xc) and the XC response (xt_xc_resp) have no host path; call "
-                                  "mf.to_device() before the SCF")
-    _g.check_ks_gradient_mf(scf, allow_rsh=allow_rsh)
     if td.method == 0:
         raise NotImplementedError("spin-flip gradients with the ALDA0 kernel (method = 0) on a functional: the "
                                   "density derivative of the ALDA0 kernel is not built (method = 2 is)")
@@ -107,42 +104,20 @@ def sf_amplitude(td, state_idx):
     return x.T / np.linalg.norm(x)
 
 
-class KSTerms:
-    """The XC hook of ``grad_elec`` for a UKS reference (LDA / GGA, collinear kernel): the response
-    potential V^resp of the reference (``DeviceEngine.fxc_response``) and the XC nuclear-derivative
-    terms (``qc.grad.grad_xc_pairs``).  ``grad_elec`` works in the labels "a" = flipped-from,
-    "b" = flipped-to; the engine keeps alpha, beta, so every density pair is put into the engine's
-    order on the way in and every potential back on the way out (``s``)."""
+class KSTerms(_c.KSTerms):
+    """The XC hook of ``grad_elec`` for a UKS reference (LDA / GGA): ``grad_common.KSTerms`` in the labels of
+    ``grad_elec``, "a" = flipped-from, "b" = flipped-to (``s``), with the coupling of the multicollinear kernel
+    (``sf_coupling``); the collinear kernel has none, and neither wv2 nor an extra pair."""
 
     def __init__(self, scf, s, timings, xc_chunk=None, mc=None):
         """``mc``: None for the collinear kernel; for the multicollinear one a dict
         with ``mf`` (the mean field of the TDA object) and ``samples`` (the sample count its roots were
         computed with)."""
-        self.scf, self.s, self.tm = scf, s, timings
-        self.mc = mc
-        self.x_s = self.wv1 = self.wv2 = None      # multicollinear: X_S, wv1 (4, G), wv2 (2, 4, G) alpha, beta
-        self.eng = scf.device_engine
-        if self.eng is None:
-            raise RuntimeError("the XC terms run on the GPU: run the SCF after mf.to_device()")
-        self.xc_chunk = xc_chunk
-        self.de_xc = None        # the XC nuclear-derivative part, set by grad()
-        self._ks = _g.ks_response(scf)
-        self.tm["xc_response_s"] = 0.0
-        self.tm["xc_response_calls"] = 0
+        self.s, self.mc = s, mc
+        super().__init__(scf, timings, xc_chunk)   # multicollinear: wv1 (4, G), wv2 (2, 4, G) alpha, beta
 
     def _order(self, pair):
         return np.asarray([pair[self.s[0]], pair[self.s[1]]])     # s is its own inverse
-
-    def _timed(self, f, *a, **kw):
-        t0 = time.perf_counter()
-        out = f(*a, **kw)
-        self.tm["xc_response_s"] += time.perf_counter() - t0
-        self.tm["xc_response_calls"] += 1
-        return out
-
-    def vxc_resp(self, dm):
-        """V^resp (2, nao, nao) of a symmetric density pair, in the labels of ``grad_elec``."""
-        return self._order(self._timed(self.eng.fxc_response, self._order(dm), want=("v",))["v"])
 
     def sf_coupling(self, x_s):
         """V_sf (nao, nao), the potential of wv1 = 2 w fxc_sf rho1[X_S], which stands next to hyb K[X] in
@@ -159,60 +134,29 @@ class KSTerms:
         torch.cuda.synchronize(eng.dev)
         self.tm["xc_sf_response_s"] = time.perf_counter() - t0
         t0 = time.perf_counter()
-        nk = 4 if eng.xctype == "GGA" else 1
-        # rho0 through the engine's own GEMM (a fixed summation order): equal calls give equal bits
-        with torch.cuda.device(eng.dev):
-            rho0 = eng.rho(np.asarray([c[:, o > 0] @ c[:, o > 0].T for c, o in zip(self.scf.mo_coeff, self.scf.mo_occ)]))
-        _, dq = sf_mc_kernel_grad(mf, out["rho1"][:nk], ns, device=eng.dev.index, rho=rho0)
-        wv2 = torch.zeros((2, 4, out["wv"].shape[1]), dtype=torch.float64, device=eng.dev)
-        wv2[:, :nk] = torch.as_tensor(dq, device=eng.dev) * eng.w
+        _, dq = sf_mc_kernel_grad(mf, out["rho1"][:self.nk], ns, device=eng.dev.index, rho=self.rho0())
+        wv2 = self._kernel_weights(dq)
         torch.cuda.synchronize(eng.dev)
         self.tm["mc_kernel_grad_s"] = time.perf_counter() - t0
         self.x_s, self.wv1, self.wv2 = np.asarray(x_s), out["wv"], wv2
         return out["v"]
 
     def vxc_resp_t(self, dm):
-        """What joins ``veff0doo``: f^xc[T], and with the multicollinear kernel V^k, the potential of
-        wv2, from the same row pass (potentials are linear in their weights)."""
+        """f^xc[T], and with the multicollinear kernel V^k, the potential of wv2, from the same row pass."""
+        return self.vxc_resp(dm) if self.mc is None else super().vxc_resp_t(dm)
+
+    def _rows_done(self, seconds):
+        self.tm["xc_sf_response_s"] += seconds
+
+    def extra_pairs(self):
+        """2 G_xc[wv1; X_S] with the multicollinear kernel: a one-channel term, run as a two-spin pair whose
+        second channel is zero."""
         if self.mc is None:
-            return self.vxc_resp(dm)
-        wv = self._timed(self.eng.fxc_response, self._order(dm), want=("wv",))["wv"]
-        t0 = time.perf_counter()
-        v = self.eng.rows_potential(wv + self.wv2)
-        self.tm["xc_sf_response_s"] += time.perf_counter() - t0
-        return self._order(v)
-
-    def vresp(self, dm):
-        """J[dm_a + dm_b] - hyb K[dm_s] + V^resp_s[dm]: what the Z-vector equations apply."""
-        t0 = time.perf_counter()
-        out = self._order(self._ks(self._order(dm)))
-        self.tm["xc_response_s"] += time.perf_counter() - t0     # J / K included: one call of the response
-        self.tm["xc_response_calls"] += 1
-        return out
-
-    def grad(self, d0, tz):
-        """G_xc[w vxc[rho0]; D0 + T + Z^S] + G_xc[wv[T + Z^S]; D0], (natm, 3); d0, tz in the labels of
-        ``grad_elec``.  With the multicollinear kernel wv2 joins wv[T + Z^S] and 2 G_xc[wv1; X_S] is
-        added: a one-channel term, run as a two-spin pair whose second channel is zero."""
+            return []
         import torch
-        from .qc import xc as _xc
-        eng = self.eng
-        d0, tz = self._order(d0), self._order(tz)
-        wv = self._timed(eng.fxc_response, tz, want=("wv",))["wv"]
-        t0 = time.perf_counter()
-        with torch.cuda.device(eng.dev):
-            h0 = _xc.eval_xc_eff_torch(self.scf.xc, eng.rho(d0), deriv=1)[1] * eng.w
-        st = {}
-        pairs = [(h0, d0 + tz), (wv, d0)]
-        if self.mc is not None:
-            h1 = torch.zeros_like(self.wv2)
-            h1[0] = 2.0 * self.wv1
-            pairs = [(h0, d0 + tz), (wv + self.wv2, d0), (h1, np.asarray([self.x_s, np.zeros_like(self.x_s)]))]
-        de = _g.grad_xc_pairs(self.scf, pairs, chunk=self.xc_chunk, stats=st)
-        self.tm["grad_xc_s"] = time.perf_counter() - t0
-        self.tm["grad_xc_stats"] = st
-        self.de_xc = de
-        return de
+        h1 = torch.zeros_like(self.wv2)
+        h1[0] = 2.0 * self.wv1
+        return [(h1, np.asarray([self.x_s, np.zeros_like(self.x_s)]))]
 
 
 OMEGA_TOL = 1e-9         # Ha: how closely the omega of the gradient's own coupling must reproduce the TDA root
@@ -251,20 +195,7 @@ def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, 
     if x_ab.shape != (orbvb.shape[1], nocca):
         raise ValueError(f"amplitude shape {x_ab.shape}, expected {(orbvb.shape[1], nocca)}")
 
-    k_lr = 0.0 if rsh is None else float(rsh[1]) - hyb
-
-    def get_jk(dms):             # J / K do not depend on which spin a density belongs to
-        dms = np.asarray(dms)
-        if k_lr != 0:            # hyb K + (alpha - hyb) K_LR; get_k_lr takes non-symmetric densities
-            vk_lr = k_lr * np.asarray(scf.get_k_lr(dms))
-            if hyb == 0:
-                return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], vk_lr
-            vj, vk = scf.get_jk(dm=dms, hermi=0)
-            return vj, hyb * vk + vk_lr
-        if hyb == 0:             # a pure functional forms no exchange
-            return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], np.zeros_like(dms)
-        vj, vk = scf.get_jk(dm=dms, hermi=0)
-        return vj, (vk if hyb == 1 else hyb * vk)
+    get_jk = _g.exchange_jk(scf, hyb, rsh)
 
     # T_alpha (occupied-occupied), T_beta (virtual-virtual), X in the AO basis
     ta = -x_ab.T @ x_ab
@@ -328,17 +259,8 @@ def grad_elec(scf, x_ab, flip, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, 
                   _g.jk_terms(0, -kw, db, db), _g.jk_terms(0, kw, dmz1doob, dmz1doob),
                   _g.jk_terms(0, -2 * kw, dmSx, dmSx),
                   (0.0, 2.0 * kw, dmAx - dmAx.T, dmAx)]        # -2 hyb vk[X_A] . (X_A[p,q] - X_A[q,p])
-    t0 = time.perf_counter()
-    st = {}
-    if rsh is None:
-        de += _g.grad_jk_device(mol, terms, device, stats=st)
-    else:                        # the same pairs as two lists: 2 Coulomb and 6 exchange pairs, two calls
-        jl, kl = _g.pair_lists(terms)
-        de += _g.grad_jk_rsh(mol, jl, kl, float(rsh[0]), hyb, float(rsh[1]), device, stats=st)
-        tm["grad_jk_full_s"], tm["grad_jk_lr_s"] = st.get("full_s"), st.get("lr_s")
-        tm["buckets_lr"] = st.get("buckets_lr", [])
-    tm["grad_jk_s"] = time.perf_counter() - t0
-    tm["buckets"] = st.get("buckets", [])
+    # one xt_grad_jk call; range-separated: the same pairs as two lists, 2 Coulomb and 6 exchange pairs, two calls
+    de += _g.grad_2e(mol, device, tm, hyb, rsh, terms=terms)
     if xc is not None:
         de += xc.grad((oo0a, oo0b), (dmz1dooa, dmz1doob))
     return de
@@ -361,77 +283,39 @@ class _SpinView:
         return self._scf.get_jk(dm=dm, hermi=hermi)
 
 
-class SFGradients:
+class SFGradients(_c.TDAGradients):
     """``SF_TDA_down(mf).nuc_grad_method()`` / ``SF_TDA_up(mf).nuc_grad_method()`` with the
-    reference's attributes (usfcis.py:261-331): ``state`` (1-based), ``cphf_conv_tol``,
-    ``cphf_max_cycle`` (the values its solver actually runs with, usfcis.py:145-148), ``atmlst``.
+    reference's attributes (usfcis.py:261-331; ``grad_common.TDAGradients``).
     A UHF reference takes method = 0; a UKS reference (LDA / GGA, pure or global hybrid, on a device)
     takes the collinear kernel, method = 2.  ``timings`` of the last gradient: ``one_electron_s``,
     ``grad_jk_s``, ``zvector_s`` / ``zvector_cycles`` / ``zvector_residual`` and, for a UKS reference,
     ``xc_response_s`` (every V^resp / wv evaluation, the Z-vector's included), ``grad_xc_s``."""
 
-    cphf_max_cycle = 500
-    cphf_conv_tol = 1e-10
-
+    _name, _not_run = "SF-TDA", RuntimeError
     _multicollinear = False      # SFU_gradient / SFD_gradient: method = 1 is accepted
 
     def __init__(self, td, *, allow_rsh=False):
-        self.base = td
-        self._scf, self.is_ks = _scf_of(td, self._multicollinear, allow_rsh)
+        super().__init__(td, *_scf_of(td, self._multicollinear, allow_rsh))
         # the multicollinear kernel is differentiated at the sample count the roots were computed with
         self.collinear_samples = None
         if td.method == 1:
             from .sf_tda import DAVIDSON_SAMPLES, EXPLICIT_SAMPLES
             self.collinear_samples = int(td.collinear_samples or (DAVIDSON_SAMPLES if td.davidson else EXPLICIT_SAMPLES))
-        self.mol = self._scf.mol
-        self.state = 1
-        self.atmlst = None
-        self.de = None
-        self.de_xc = None        # the XC nuclear-derivative part of the last gradient (UKS reference)
-        self.xc_chunk = None     # grid points per xt_grad_xc call; None: qc.grad.default_xc_chunk
-        self.timings = {}
 
-    def grad_nuc(self, mol=None, atmlst=None):
-        return _g.grad_nuc(mol or self.mol, atmlst)
+    def _davidson(self):
+        return self.base.davidson
 
-    def grad_elec(self, atmlst=None):
+    def _amplitudes(self):
+        return sf_amplitude(self.base, self.state - 1)
+
+    def _ks_terms(self):
         td = self.base
-        if getattr(td, "v", None) is None:
-            raise RuntimeError("run the SF-TDA kernel() first")
-        if not 1 <= self.state <= np.asarray(td.v).shape[1]:
-            raise ValueError(f"state {self.state} is not among the computed roots")
-        conv = getattr(td, "converged", None)
-        if td.davidson and conv is not None and not bool(np.asarray(conv)[self.state - 1]):
-            raise RuntimeError(f"root {self.state} of the Davidson solve is not converged")
-        dev = getattr(self._scf, "_device", None)
-        if dev is None:
-            raise RuntimeError("the gradient runs on the GPU (xt_grad_jk, device J / K): call "
-                               "mf.to_device() before the SCF")
-        flip = td.isf == 1
-        if self.is_ks:
-            self.timings.clear()
-            mc = dict(mf=td.mf, samples=self.collinear_samples) if td.method == 1 else None
-            xc = KSTerms(self._scf, (1, 0) if flip else (0, 1), self.timings, self.xc_chunk, mc=mc)
-            omega = float(getattr(self._scf, "omega", 0.0))
-            rsh = (omega, float(self._scf.alpha)) if omega != 0 else None
-            root = float(np.asarray(td.e)[self.state - 1]) if rsh is not None else None
-            de = grad_elec(self._scf, sf_amplitude(td, self.state - 1), flip, dev, self.cphf_conv_tol,
-                           self.cphf_max_cycle, self.timings, hyb=float(self._scf.hyb), xc=xc, rsh=rsh, root=root)
-            self.de_xc = xc.de_xc
-        else:
-            de = grad_elec(self._scf, sf_amplitude(td, self.state - 1), flip, dev, self.cphf_conv_tol,
-                           self.cphf_max_cycle, self.timings)
-        return de if atmlst is None else de[list(atmlst)]
+        mc = dict(mf=td.mf, samples=self.collinear_samples) if td.method == 1 else None
+        return KSTerms(self._scf, (1, 0) if td.isf == 1 else (0, 1), self.timings, self.xc_chunk, mc=mc)
 
-    def kernel(self, state=None, atmlst=None):
-        if state is not None:
-            self.state = state
-        if atmlst is None:
-            atmlst = self.atmlst
-        else:
-            self.atmlst = atmlst
-        self.de = self.grad_elec(atmlst) + self.grad_nuc(atmlst=atmlst)
-        return self.de
+    def _grad_elec(self, x, device, **kw):
+        return grad_elec(self._scf, x, self.base.isf == 1, device, self.cphf_conv_tol, self.cphf_max_cycle,
+                         self.timings, **kw)
 
 
 class _SFKernelGradient(SFGradients):

@@ -45,7 +45,10 @@ Refused with NotImplementedError: an ROKS / ROHF mean field (X-TDA: the referenc
 Range-separated hybrids come in through ``td.Gradients(state=1)``, which constructs
 ``UTDAGradients(td, allow_rsh=True)``: -hyb K above becomes -(hyb K + (alpha - hyb) K_LR) everywhere, and the
 exchange list goes once through ``xt_grad_jk2`` weighted by hyb and once through ``xt_grad_jk2_lr`` weighted
-by alpha - hyb (``qc.grad.grad_jk_rsh``).  ``nuc_grad_method()`` keeps refusing them.
+by alpha - hyb (``qc.grad.grad_2e``: ``grad_jk_rsh``).  ``nuc_grad_method()`` keeps refusing them.
+
+The driver object, the XC hook and the resolution of the reference are shared with the spin-flip gradients:
+``UTDAGradients``, ``KSTerms`` and ``_scf_of`` build on ``grad_common``.
 """
 from __future__ import annotations
 
@@ -53,6 +56,7 @@ import time
 
 import numpy as np
 
+from . import grad_common as _c
 from .qc import grad as _g
 
 
@@ -66,20 +70,11 @@ def _scf_of(td, allow_rsh=False):
                                   "rotations the U-TDA formula assumes; use a UHF / UKS reference")
     if td.basis == 'tensor':
         raise NotImplementedError("U-TDA gradients need basis='orbital': the tensor-basis solver is not built")
-    ref = mf.extra.get("qc_scf") if hasattr(mf, "extra") else None
-    scf = ref() if ref is not None else None          # a weak reference: the mean field does not own the SCF
+    scf = _c.scf_behind(mf)
     if scf is None:
         raise ValueError("the gradient needs the SCF object the mean field came from (qc UHF / UKS .to_meanfield()), "
                          "still alive")
-    if str(getattr(scf, "xc", "HF")).upper() == "HF":
-        _g.check_gradient_mf(scf)
-        return scf, False
-    if getattr(scf, "_device", None) is None:
-        raise NotImplementedError(f"U-TDA gradients for xc = {scf.xc!r} on the host: the XC derivative (xt_grad_xc) "
-                                  "and the XC response (xt_xc_resp) have no host path; call mf.to_device() before "
-                                  "the SCF")
-    _g.check_ks_gradient_mf(scf, allow_rsh=allow_rsh)
-    return scf, True
+    return scf, _c.check_reference(scf, "U-TDA", allow_rsh)
 
 
 def utda_amplitudes(td, state_idx):
@@ -97,78 +92,32 @@ def utda_amplitudes(td, state_idx):
     return xa.T / nrm, xb.T / nrm
 
 
-class KSTerms:
-    """The XC terms of ``grad_elec`` on a UKS reference (LDA / GGA), everything in the order alpha, beta:
-    the response potential and weights of the reference (``DeviceEngine.fxc_response``), the
-    third-derivative weights wv2 (``qc.xc.kernel_grad_torch``) and the XC nuclear-derivative terms
-    (``qc.grad.grad_xc_pairs``)."""
-
-    def __init__(self, scf, timings, xc_chunk=None):
-        self.scf, self.tm = scf, timings
-        self.eng = scf.device_engine
-        if self.eng is None:
-            raise RuntimeError("the XC terms run on the GPU: run the SCF after mf.to_device()")
-        self.xc_chunk = xc_chunk
-        self.de_xc = None
-        self.x_s = self.wv1 = self.wv2 = None
-        self.vresp = self._count(_g.ks_response(scf))     # J - hyb K + V^resp: one call of the response
-        self.tm["xc_response_s"] = 0.0
-        self.tm["xc_response_calls"] = 0
-
-    def _count(self, f):
-        def timed(*a, **kw):
-            t0 = time.perf_counter()
-            out = f(*a, **kw)
-            self.tm["xc_response_s"] += time.perf_counter() - t0
-            self.tm["xc_response_calls"] += 1
-            return out
-        return timed
+class KSTerms(_c.KSTerms):
+    """The XC terms of ``grad_elec`` on a UKS reference (LDA / GGA): ``grad_common.KSTerms`` in the order
+    alpha, beta, with the coupling of the reference's own kernel and its third-derivative weights wv2
+    (``qc.xc.kernel_grad_torch``); the extra pair is G_xc[2 wv[X_S]; X_S]."""
 
     def coupling(self, x_s):
         """V^resp (2, nao, nao) of the symmetric transition densities X_S; keeps wv1 = wv[X_S] and
         wv2 = w d(rho1^T fxc rho1) / d rho0 for ``vxc_resp_t`` and ``grad``."""
         import torch
         from .qc import xc as _xc
-        eng = self.eng
-        out = self._count(eng.fxc_response)(x_s, want=("v", "wv", "rho1"))
+        eng, nk = self.eng, self.nk
+        out = self._timed(eng.fxc_response, x_s, want=("v", "wv", "rho1"))
         t0 = time.perf_counter()
-        nk = 4 if eng.xctype == "GGA" else 1
         with torch.cuda.device(eng.dev):
-            # rho0 through the engine's own GEMM (a fixed summation order): equal calls give equal bits
-            rho0 = eng.rho(np.asarray([c[:, o > 0] @ c[:, o > 0].T for c, o in zip(self.scf.mo_coeff, self.scf.mo_occ)]))
-            _, dq = _xc.kernel_grad_torch(self.scf.xc, rho0[:, :nk], out["rho1"][:, :nk])
-            wv2 = torch.zeros_like(out["wv"])
-            wv2[:, :nk] = dq * eng.w
+            _, dq = _xc.kernel_grad_torch(self.scf.xc, self.rho0()[:, :nk], out["rho1"][:, :nk])
+            wv2 = self._kernel_weights(dq)
         torch.cuda.synchronize(eng.dev)
         self.tm["kernel_grad_s"] = time.perf_counter() - t0
         self.x_s, self.wv1, self.wv2 = np.asarray(x_s), out["wv"], wv2
         return out["v"]
 
-    def vxc_resp_t(self, dm):
-        """f^xc[T] and the potential of wv2, from one row pass (potentials are linear in their weights)."""
-        wv = self._count(self.eng.fxc_response)(np.asarray(dm), want=("wv",))["wv"]
-        t0 = time.perf_counter()
-        v = self.eng.rows_potential(wv + self.wv2)
-        self.tm["xc_rows_s"] = time.perf_counter() - t0
-        return v
+    def _rows_done(self, seconds):
+        self.tm["xc_rows_s"] = seconds
 
-    def grad(self, d0, tz):
-        """G_xc[w vxc[rho0]; D0 + T + Z^S] + G_xc[wv[T + Z^S] + wv2; D0] + G_xc[2 wv[X_S]; X_S], (natm, 3)."""
-        import torch
-        from .qc import xc as _xc
-        eng = self.eng
-        d0, tz = np.asarray(d0), np.asarray(tz)
-        wv = self._count(eng.fxc_response)(tz, want=("wv",))["wv"]
-        t0 = time.perf_counter()
-        with torch.cuda.device(eng.dev):
-            h0 = _xc.eval_xc_eff_torch(self.scf.xc, eng.rho(d0), deriv=1)[1] * eng.w
-        st = {}
-        pairs = [(h0, d0 + tz), (wv + self.wv2, d0), (2.0 * self.wv1, self.x_s)]
-        de = _g.grad_xc_pairs(self.scf, pairs, chunk=self.xc_chunk, stats=st)
-        self.tm["grad_xc_s"] = time.perf_counter() - t0
-        self.tm["grad_xc_stats"] = st
-        self.de_xc = de
-        return de
+    def extra_pairs(self):
+        return [(2.0 * self.wv1, self.x_s)]
 
 
 def jk_lists(d, tz, xt, hyb):
@@ -192,16 +141,16 @@ def jk_lists(d, tz, xt, hyb):
     return jl, kl
 
 
-def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None, hyb=1.0, xc=None, one_call=True,
-              rsh=None, root=None):
+def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=None, hyb=1.0, xc=None, rsh=None,
+              root=None):
     """Electronic part of the gradient of E_SCF + omega, (natm, 3).  ``x`` = (X_a, X_b), each
     (nvir_s, nocc_s); ``hyb``: the fraction of exact exchange (1 for Hartree-Fock); ``xc``: the XC terms
-    of a UKS reference (``KSTerms``), None for Hartree-Fock.  ``one_call``: the two-electron derivative
-    term as one ``xt_grad_jk2`` call; False sends the same pairs as two ``xt_grad_jk`` calls.
+    of a UKS reference (``KSTerms``), None for Hartree-Fock.  The two-electron derivative term is one
+    ``xt_grad_jk2`` call.
     ``rsh``: (omega, alpha) of a range-separated hybrid: every K below is hyb K + (alpha - hyb) K_LR
-    (``get_jk`` here, ``qc.grad.ks_response`` in the Z-vector) and the exchange list goes once per operator
-    (``qc.grad.grad_jk_rsh``); ``root``: the TDA root (Ha) of these amplitudes, checked against the omega of
-    the coupling formed here (``grad.check_root``)."""
+    (``qc.grad.exchange_jk`` here, ``qc.grad.ks_response`` in the Z-vector) and the exchange list goes once per
+    operator (``qc.grad.grad_2e``: ``grad_jk_rsh``); ``root``: the TDA root (Ha) of these amplitudes, checked
+    against the omega of the coupling formed here (``grad.check_root``)."""
     tm = {} if timings is None else timings
     mol = scf.mol
     C = [np.asarray(scf.mo_coeff[s]) for s in range(2)]
@@ -216,20 +165,7 @@ def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=N
         if x[s].shape != (v[s].shape[1], no[s]):
             raise ValueError(f"amplitude shape {x[s].shape}, expected {(v[s].shape[1], no[s])}")
 
-    k_lr = 0.0 if rsh is None else float(rsh[1]) - hyb
-
-    def get_jk(dms):
-        dms = np.asarray(dms)
-        if k_lr != 0:            # hyb K + (alpha - hyb) K_LR; get_k_lr takes non-symmetric densities
-            vk_lr = k_lr * np.asarray(scf.get_k_lr(dms))
-            if hyb == 0:
-                return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], vk_lr
-            vj, vk = scf.get_jk(dm=dms, hermi=0)
-            return vj, hyb * vk + vk_lr
-        if hyb == 0:             # a pure functional forms no exchange
-            return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], np.zeros_like(dms)
-        vj, vk = scf.get_jk(dm=dms, hermi=0)
-        return vj, (vk if hyb == 1 else hyb * vk)
+    get_jk = _g.exchange_jk(scf, hyb, rsh)
 
     too = [-x[s].T @ x[s] for s in range(2)]
     tvv = [x[s] @ x[s].T for s in range(2)]
@@ -280,91 +216,35 @@ def grad_elec(scf, x, device, cphf_conv_tol=1e-10, cphf_max_cycle=500, timings=N
     t0 = time.perf_counter()
     de = _g.contract_1e(mol, _g.hcore_generator(mol), _g.get_ovlp(mol), (d0 + tz).sum(axis=0), im0)
     tm["one_electron_s"] = time.perf_counter() - t0
-    jl, kl = jk_lists(d0 + tz, tz, xt, hyb if rsh is None else 1.0)
-    t0 = time.perf_counter()
-    st = {}
-    if rsh is not None:          # the pairs of full exchange, weighted per operator: two calls
-        de += _g.grad_jk_rsh(mol, jl, kl, float(rsh[0]), hyb, float(rsh[1]), device, stats=st)
-        tm["grad_jk_full_s"], tm["grad_jk_lr_s"] = st.get("full_s"), st.get("lr_s")
-        tm["buckets_lr"] = st.get("buckets_lr", [])
-    elif one_call:
-        de += _g.grad_jk_lists(mol, jl, kl, device, stats=st)
-    else:
-        for terms in two_call_terms(jl, kl):
-            de += _g.grad_jk_device(mol, terms, device, stats=st)
-    tm["grad_jk_s"] = time.perf_counter() - t0
-    tm["buckets"] = st.get("buckets", [])
+    # range-separated: the pairs of full exchange, weighted per operator, two calls
+    lists = jk_lists(d0 + tz, tz, xt, hyb if rsh is None else 1.0)
+    de += _g.grad_2e(mol, device, tm, hyb, rsh, lists=lists)
     if xc is not None:
         de += xc.grad(d0, tz)
     return de
 
 
-def two_call_terms(jl, kl):
-    """The pairs of ``jk_lists`` as the terms of ``xt_grad_jk`` calls of at most eight pairs each (every
-    pair with one zero weight): what a gradient without ``xt_grad_jk2`` would have to send."""
-    terms = [(w, 0.0, p, q) for w, p, q in jl] + [(0.0, w, p, q) for w, p, q in kl]
-    return [terms[i:i + _g.MAX_TERMS] for i in range(0, len(terms), _g.MAX_TERMS)]
-
-
-class UTDAGradients:
+class UTDAGradients(_c.TDAGradients):
     """``XTDA(mol, mf).nuc_grad_method()`` on a UHF or UKS (LDA / GGA, pure or global hybrid, on a
-    device) reference, with the attributes of ``grad.SFGradients``: ``state`` (1-based),
-    ``cphf_conv_tol``, ``cphf_max_cycle``, ``atmlst``, ``xc_chunk``, ``de``.  ``timings`` of the last
-    gradient: ``one_electron_s``, ``grad_jk_s`` and ``buckets``, ``zvector_s`` / ``zvector_cycles`` /
-    ``zvector_residual`` and, on a UKS reference, ``xc_response_s`` / ``xc_response_calls`` (every
-    V^resp / wv evaluation, the Z-vector's included), ``kernel_grad_s`` (the third-derivative weights),
-    ``xc_rows_s`` and ``grad_xc_s``."""
+    device) reference, with the attributes of ``grad.SFGradients`` (``grad_common.TDAGradients``).
+    ``timings`` of the last gradient: ``one_electron_s``, ``grad_jk_s`` and ``buckets``, ``zvector_s`` /
+    ``zvector_cycles`` / ``zvector_residual`` and, on a UKS reference, ``xc_response_s`` /
+    ``xc_response_calls`` (every V^resp / wv evaluation, the Z-vector's included), ``kernel_grad_s`` (the
+    third-derivative weights), ``xc_rows_s`` and ``grad_xc_s``."""
 
-    cphf_max_cycle = 500
-    cphf_conv_tol = 1e-10
+    _name, _not_run = "XTDA", ValueError
 
     def __init__(self, td, *, allow_rsh=False):
-        self.base = td
-        self._scf, self.is_ks = _scf_of(td, allow_rsh)
-        self.mol = self._scf.mol
-        self.state = 1
-        self.atmlst = None
-        self.de = None
-        self.de_xc = None        # the XC nuclear-derivative part of the last gradient (UKS reference)
-        self.xc_chunk = None     # grid points per xt_grad_xc call; None: qc.grad.default_xc_chunk
-        self.timings = {}
+        super().__init__(td, *_scf_of(td, allow_rsh))
 
-    def grad_nuc(self, mol=None, atmlst=None):
-        return _g.grad_nuc(mol or self.mol, atmlst)
+    def _davidson(self):
+        return self.base.use_Davidson
 
-    def grad_elec(self, atmlst=None):
-        td = self.base
-        if getattr(td, "v", None) is None:
-            raise ValueError("run the XTDA kernel() first")
-        if not 1 <= self.state <= np.asarray(td.v).shape[1]:
-            raise ValueError(f"state {self.state} is not among the computed roots")
-        conv = getattr(td, "converged", None)
-        if td.use_Davidson and conv is not None and not bool(np.asarray(conv)[self.state - 1]):
-            raise RuntimeError(f"root {self.state} of the Davidson solve is not converged")
-        dev = getattr(self._scf, "_device", None)
-        if dev is None:
-            raise RuntimeError("the gradient runs on the GPU (xt_grad_jk2, device J / K): call "
-                               "mf.to_device() before the SCF")
-        self.timings.clear()
-        x = utda_amplitudes(td, self.state - 1)
-        if self.is_ks:
-            xc = KSTerms(self._scf, self.timings, self.xc_chunk)
-            omega = float(getattr(self._scf, "omega", 0.0))
-            rsh = (omega, float(self._scf.alpha)) if omega != 0 else None
-            root = float(np.asarray(td.e)[self.state - 1]) if rsh is not None else None
-            de = grad_elec(self._scf, x, dev, self.cphf_conv_tol, self.cphf_max_cycle, self.timings,
-                           hyb=float(self._scf.hyb), xc=xc, rsh=rsh, root=root)
-            self.de_xc = xc.de_xc
-        else:
-            de = grad_elec(self._scf, x, dev, self.cphf_conv_tol, self.cphf_max_cycle, self.timings)
-        return de if atmlst is None else de[list(atmlst)]
+    def _amplitudes(self):
+        return utda_amplitudes(self.base, self.state - 1)
 
-    def kernel(self, state=None, atmlst=None):
-        if state is not None:
-            self.state = state
-        if atmlst is None:
-            atmlst = self.atmlst
-        else:
-            self.atmlst = atmlst
-        self.de = self.grad_elec(atmlst) + self.grad_nuc(atmlst=atmlst)
-        return self.de
+    def _ks_terms(self):
+        return KSTerms(self._scf, self.timings, self.xc_chunk)
+
+    def _grad_elec(self, x, device, **kw):
+        return grad_elec(self._scf, x, device, self.cphf_conv_tol, self.cphf_max_cycle, self.timings, **kw)

@@ -18,6 +18,9 @@
   (``xt_grad_jk2``), for the two-particle densities of more than eight pairs (``xtddft_amd/grad_utda.py``);
 * ``grad_jk_rsh`` -- the two calls of a range-separated hybrid: ``xt_grad_jk2`` with hyb on the exchange
   list and ``xt_grad_jk2_lr`` (erf(omega r12) / r12) with alpha - hyb on the same pairs;
+* ``grad_2e`` -- the one place that chooses among the three above and fills the timing keys, for the ground
+  states here and the excited-state drivers; ``exchange_jk`` -- J and hyb K + (alpha - hyb) K_LR of
+  non-symmetric densities, the ``get_jk`` of both excited-state ``grad_elec``;
 * ``solve_zvector`` -- the UCPHF Z-vector equations (usfcis.py:127-150) by a host-driven
   preconditioned GMRES whose response J / K come from ``DeviceEngine.get_jk``;
 * ``Gradients`` -- ``UHF.nuc_grad_method()``: the T = Z = X = 0 subset of the excited-state
@@ -375,6 +378,52 @@ def grad_jk_rsh(mol, jterms, kterms, omega, hyb, alpha, device: int = 0, strip=N
     return de
 
 
+def grad_2e(mol, device, timings, hyb=1.0, rsh=None, *, terms=None, lists=None):
+    """(natm, 3): the two-electron derivative term of every gradient driver, given either as ``terms`` =
+    [(wj, wk, P, Q)] or as ``lists`` = (Coulomb list, exchange list).  Without range separation the terms go
+    through ``grad_jk_device`` (``xt_grad_jk``) and the lists through ``grad_jk_lists`` (``xt_grad_jk2``), with
+    ``hyb`` already in their exchange weights.  ``rsh`` = (omega, alpha): the exchange weights are those of full
+    exchange and either form goes as two lists through ``grad_jk_rsh``, which weights them with ``hyb`` and
+    alpha - hyb.  ``timings`` receives ``grad_jk_s`` and ``buckets`` and, with ``rsh``, ``grad_jk_full_s``,
+    ``grad_jk_lr_s`` and ``buckets_lr``."""
+    t0 = time.perf_counter()
+    st = {}
+    if rsh is not None:
+        jl, kl = pair_lists(terms) if lists is None else lists
+        de = grad_jk_rsh(mol, jl, kl, float(rsh[0]), hyb, float(rsh[1]), device, stats=st)
+        timings["grad_jk_full_s"], timings["grad_jk_lr_s"] = st.get("full_s"), st.get("lr_s")
+        timings["buckets_lr"] = st.get("buckets_lr", [])
+    elif lists is None:
+        de = grad_jk_device(mol, terms, device, stats=st)
+    else:
+        de = grad_jk_lists(mol, *lists, device, stats=st)
+    timings["grad_jk_s"] = time.perf_counter() - t0
+    timings["buckets"] = st.get("buckets", [])
+    return de
+
+
+def exchange_jk(scf, hyb, rsh=None):
+    """``get_jk(dms)`` -> (J, the exchange of the functional) of a stack of densities that need not be
+    symmetric: hyb K and, with ``rsh`` = (omega, alpha) of a range-separated hybrid, hyb K + (alpha - hyb) K_LR
+    (``scf.get_k_lr``).  hyb = 0 forms no full-range exchange (``with_k=False``).  J / K do not depend on
+    which spin a density belongs to."""
+    k_lr = 0.0 if rsh is None else float(rsh[1]) - hyb
+
+    def get_jk(dms):
+        dms = np.asarray(dms)
+        if k_lr != 0:            # get_k_lr takes non-symmetric densities
+            vk_lr = k_lr * np.asarray(scf.get_k_lr(dms))
+            if hyb == 0:
+                return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], vk_lr
+            vj, vk = scf.get_jk(dm=dms, hermi=0)
+            return vj, hyb * vk + vk_lr
+        if hyb == 0:             # a pure functional forms no exchange
+            return scf.get_jk(dm=dms, hermi=0, with_k=False)[0], np.zeros_like(dms)
+        vj, vk = scf.get_jk(dm=dms, hermi=0)
+        return vj, (vk if hyb == 1 else hyb * vk)
+    return get_jk
+
+
 # ------------------------------------------------------------------ Z-vector
 def gmres(aop, b, precond, tol, max_cycle):
     """Solve aop(x) = b by left-preconditioned full GMRES from x = 0; returns (x, residual norm
@@ -498,12 +547,19 @@ def check_gradient_mf(mf):
     if xc != "HF":
         raise NotImplementedError(f"nuclear gradients for xc = {mf.xc!r}: the XC derivative terms are not built "
                                   "(Hartree-Fock only)")
+    _check_exact_integrals(mf)
+
+
+def _check_exact_integrals(mf):
+    """The last refusals of both ``check_gradient_mf`` and ``check_ks_gradient_mf``: density fitting, X2C and
+    a loose Cholesky factor."""
     if getattr(mf, "with_df", None) is not None:
         raise NotImplementedError("nuclear gradients for density-fitted mean fields")
     if getattr(mf, "with_x2c", None) is not None:
         raise NotImplementedError("nuclear gradients with the X2C core Hamiltonian")
     # J / K from the integral-direct Cholesky factor are exact to chol_tol only, while xt_grad_jk
-    # differentiates the exact integrals: a loose factor would give a non-variational gradient
+    # differentiates the exact integrals: a loose factor would give a non-variational gradient; the
+    # long-range factor of a range-separated functional is built at the same chol_tol
     uses_chol = getattr(mf, "cderi_exact", None) is not None or getattr(mf, "eri_mode", "") == "cholesky"
     if uses_chol and float(getattr(mf, "chol_tol", 0.0)) > MAX_CHOL_TOL:
         raise ValueError(f"nuclear gradients need J / K of the exact integrals: Cholesky tolerance "
@@ -533,12 +589,15 @@ class Gradients:
     part is one ``xt_grad_jk`` call on the mean field's device (``mf.to_device()``)."""
 
     def __init__(self, mf):
-        check_gradient_mf(mf)
+        self._check_mf(mf)
         self.base = mf
         self.mol = mf.mol
         self.atmlst = None
         self.de = None
         self.timings = {}
+
+    def _check_mf(self, mf):
+        check_gradient_mf(mf)
 
     def get_ovlp(self, mol=None):
         return get_ovlp(mol or self.mol)
@@ -556,7 +615,9 @@ class Gradients:
                                "before kernel()")
         return dev
 
-    def grad_elec(self, atmlst=None):
+    def _one_electron(self):
+        """(the device, D_a, D_b, the one-electron and overlap part (natm, 3)) of a converged mean field: the
+        energy-weighted density is that of ``mf._veff``, which on a UKS holds V_xc + J - hyb K."""
         mf, mol = self.base, self.mol
         if mf.mo_coeff is None:
             raise RuntimeError("run the SCF first")
@@ -568,11 +629,11 @@ class Gradients:
         t0 = time.perf_counter()
         de = contract_1e(mol, hcore_generator(mol), get_ovlp(mol), d0a + d0b, w)
         self.timings["one_electron_s"] = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        st = {}
-        de += grad_jk_device(mol, ground_terms(d0a, d0b), dev, stats=st)
-        self.timings["grad_jk_s"] = time.perf_counter() - t0
-        self.timings["buckets"] = st.get("buckets", [])
+        return dev, d0a, d0b, de
+
+    def grad_elec(self, atmlst=None):
+        dev, d0a, d0b, de = self._one_electron()
+        de += grad_2e(self.mol, dev, self.timings, terms=ground_terms(d0a, d0b))
         return de if atmlst is None else de[list(atmlst)]
 
     def kernel(self, atmlst=None):
@@ -739,15 +800,7 @@ def check_ks_gradient_mf(mf, *, allow_rsh=False):
                                   "the .Gradients() entry of the same object (nuc_grad_method() stays as it was)")
     if getattr(mf, "nlc", None) is not None:
         raise NotImplementedError("nuclear gradients with VV10 non-local correlation: its derivative is not built")
-    if getattr(mf, "with_df", None) is not None:
-        raise NotImplementedError("nuclear gradients for density-fitted mean fields")
-    if getattr(mf, "with_x2c", None) is not None:
-        raise NotImplementedError("nuclear gradients with the X2C core Hamiltonian")
-    # the long-range factor of a range-separated functional is built at the same chol_tol
-    uses_chol = getattr(mf, "cderi_exact", None) is not None or getattr(mf, "eri_mode", "") == "cholesky"
-    if uses_chol and float(getattr(mf, "chol_tol", 0.0)) > MAX_CHOL_TOL:
-        raise ValueError(f"nuclear gradients need J / K of the exact integrals: Cholesky tolerance "
-                         f"{mf.chol_tol:g} is above {MAX_CHOL_TOL:g}")
+    _check_exact_integrals(mf)
 
 
 class KSGradients(Gradients):
@@ -759,14 +812,19 @@ class KSGradients(Gradients):
     atom-centred grid by the weight derivatives, which vanish with the grid error."""
 
     def __init__(self, mf, *, allow_rsh=False):
-        check_ks_gradient_mf(mf, allow_rsh=allow_rsh)
-        self.base = mf
-        self.mol = mf.mol
-        self.atmlst = None
-        self.de = None
+        self._allow_rsh = allow_rsh
+        super().__init__(mf)
         self.de_xc = None        # the XC part of the last gradient, (natm, 3)
-        self.timings = {}
         self.xc_chunk = None     # grid points per xt_grad_xc call; None: default_xc_chunk
+
+    def _check_mf(self, mf):
+        check_ks_gradient_mf(mf, allow_rsh=self._allow_rsh)
+
+    def _device(self):
+        dev = super()._device()
+        if getattr(self.base, "device_engine", None) is None:
+            raise RuntimeError("the XC gradient runs on the GPU (xt_grad_xc): run the SCF after mf.to_device()")
+        return dev
 
     @property
     def grid_response(self):
@@ -778,31 +836,13 @@ class KSGradients(Gradients):
             raise NotImplementedError("grid_response = True: the derivatives of the grid weights are not built")
 
     def grad_elec(self, atmlst=None):
-        mf, mol = self.base, self.mol
-        if mf.mo_coeff is None:
-            raise RuntimeError("run the SCF first")
-        dev = self._device()
-        if getattr(mf, "device_engine", None) is None:
-            raise RuntimeError("the XC gradient runs on the GPU (xt_grad_xc): run the SCF after mf.to_device()")
-        orboa, _, orbob, _, fa, fb = uhf_orbitals(mf)      # mf._veff of a UKS is V_xc + J - hyb K
-        nocca, noccb = orboa.shape[1], orbob.shape[1]
-        d0a, d0b = orboa @ orboa.T, orbob @ orbob.T
-        w = orboa @ fa[:nocca, :nocca] @ orboa.T + orbob @ fb[:noccb, :noccb] @ orbob.T
-        t0 = time.perf_counter()
-        de = contract_1e(mol, hcore_generator(mol), get_ovlp(mol), d0a + d0b, w)
-        self.timings["one_electron_s"] = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        st = {}
+        mf = self.base
+        dev, d0a, d0b, de = self._one_electron()
         omega = float(getattr(mf, "omega", 0.0))
-        if omega != 0:           # hyb K + (alpha - hyb) K_LR: the exchange pairs once per operator
-            jl, kl = pair_lists(ks_ground_terms(d0a, d0b, 1.0))
-            de += grad_jk_rsh(mol, jl, kl, omega, float(mf.hyb), float(mf.alpha), dev, stats=st)
-            self.timings["grad_jk_full_s"], self.timings["grad_jk_lr_s"] = st.get("full_s"), st.get("lr_s")
-            self.timings["buckets_lr"] = st.get("buckets_lr", [])
-        else:
-            de += grad_jk_device(mol, ks_ground_terms(d0a, d0b, mf.hyb), dev, stats=st)
-        self.timings["grad_jk_s"] = time.perf_counter() - t0
-        self.timings["buckets"] = st.get("buckets", [])
+        # range-separated, hyb K + (alpha - hyb) K_LR: the pairs of full exchange, weighted once per operator
+        rsh = (omega, float(mf.alpha)) if omega != 0 else None
+        terms = ks_ground_terms(d0a, d0b, mf.hyb if rsh is None else 1.0)
+        de += grad_2e(self.mol, dev, self.timings, float(mf.hyb), rsh, terms=terms)
         t0 = time.perf_counter()
         sx = {}
         self.de_xc = grad_xc_device(mf, d0a, d0b, chunk=self.xc_chunk, stats=sx)
